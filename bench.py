@@ -5,19 +5,27 @@ One "step" = one optimizer iteration t of the reference schedule (tree build +
 BH repulsion + attraction + fused gains/momentum update + centring) of the
 device-resident loop; the embedding, P and all state stay in HBM.
 
-Timeline of a run:
+Timeline of a plain run (`bench.py --gpus 1 --steps K --warmup W`):
   setup    synthetic data on the device, kNN, affinities, symmetrisation,
            seeded init, tsne_dev_opt_setup -- each timed;
-  warmup   W iterations (t = 1..W) on a snapshot of the initial state, with
-           the per-stage profile and BH work counters ON (they describe the
-           first W iterations of the timed window); the snapshot is restored;
-  window   `value`: EXACTLY K iterations t = 1..K timed between barriers +
-           synchronisations (no profiling inside; the attraction kernel's HIP
-           events are recorded on its own stream and read afterwards);
-  rest     the remaining iterations t = K+1..T of the schedule (per-iteration
-           cost varies by >1000x over a run: SURVEY.md 8a row A15), profiled
-           every --trace iterations -> `full_schedule_it_s` = T / (window + rest)
-           and `end_to_end_s` = setup + whole schedule + D2H of Y and the losses.
+  warmup   W steps (the schedule's first W steps of T/K iterations each, from
+           t = 1 again after the K-th) on a snapshot of the initial state; the
+           snapshot is restored;
+  timed    `value` = T / loop seconds: the whole schedule t = 1..T as K steps of
+           T/K iterations between barriers + synchronisations (no profiling
+           inside; the attraction kernel's HIP events are recorded on its own
+           stream and read afterwards); `ms_per_step` = loop / K.  K > T makes
+           the schedule K iterations long, so --steps is always the number of
+           timed steps;
+  outputs  with --dump-outputs DIR, what the timed schedule left in the
+           caller's buffers (Y, update, gains) and its losses, as DIR/<name>.npy;
+  line     one JSON result line on stdout.
+
+--full adds every other leg, each after the timed region: the trace pass (the
+schedule again, profiled every --trace iterations: per-stage times and BH work
+counters), the CPU baseline (the oracle on snapshots of that pass), the
+end-to-end leg through the native CLI, the committed PMC summaries quoted in
+the line, and the side file of per-iteration detail (--detail-out).
 
 Multi-GPU: launched by torch.distributed.run, one process per GPU; the
 library's own RCCL communicator carries the per-iteration all-gathers;
@@ -60,9 +68,17 @@ def parse():
                          "embedding (octree); c5: 50,000-point precomputed distance matrix "
                          "(--inputDistanceMatrix: affinities + joint + optimizer, no kNN)")
     ap.add_argument("--steps", type=int, default=20,
-                    help="the timed schedule t=1..T as K steps of T/K iterations (0 = one step per iteration)")
+                    help="the timed schedule t=1..T as K steps of T/K iterations (0 = one step per iteration; "
+                         "K > T lengthens the schedule to K iterations)")
     ap.add_argument("--warmup", type=int, default=5,
-                    help="untimed warmup: the first W steps of the schedule on a restored snapshot")
+                    help="untimed warmup: W steps of the schedule, from its first, on a restored snapshot")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs a plain run leaves out: the trace pass (--trace), the CPU baseline, "
+                         "the end-to-end leg through the native CLI, the PMC summaries and the detail side file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64): Y, update, "
+                         "gains (a seeded row sample, its indices in rows.npy, where they exceed 60 MB) and "
+                         "loss_iterations / losses")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--k", type=int, default=90)
@@ -70,10 +86,12 @@ def parse():
     ap.add_argument("--theta", type=float, default=0.5)
     ap.add_argument("--iterations", type=int, default=1000, help="schedule length T")
     ap.add_argument("--trace", type=int, default=50,
-                    help="trace pass after the timed region: profile t=1..5 and every N-th iteration (0 = no pass)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: trace pass after the timed region: profile t=1..5 and every N-th iteration "
+                         "(0 = no pass)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-cli-e2e", action="store_true",
-                    help="skip the end-to-end leg through the native CLI from the reference's COO input (C3, N=1)")
+                    help="--full without the end-to-end leg through the native CLI from the reference's COO input "
+                         "(C3, N=1)")
     ap.add_argument("--cpu-sample", type=int, default=64, help="queries in the CPU baseline sample")
     ap.add_argument("--cpu-knn-sample", type=int, default=32, help="queries in the CPU baseline kNN sample")
     ap.add_argument("--dump-y", default="", help="comma-separated iterations t: save Y as <dump-dir>/Y_t<t>.npy")
@@ -84,14 +102,20 @@ def parse():
     ap.add_argument("--y0-seed", type=int, default=0, help="initWorkingSet seed (the reference is unseeded)")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE",
                     help="tsne_ctx_set_option on the bench's context (A/B of a tunable; repeatable)")
-    ap.add_argument("--detail-out", default="gpurun_out/bench_detail.json",
-                    help="side file for the per-iteration timeline, attraction launch log and PMC blobs "
-                         "(the stdout line stays < 8 KB; '' = none)")
+    ap.add_argument("--detail-out", default=None,
+                    help="side file for the per-iteration timeline, attraction launch log and PMC blobs (the stdout "
+                         "line stays < 8 KB; default: bench_detail.json under --dump-dir with --full, none without; "
+                         "'' = none)")
     ap.add_argument("--cpu-budget", type=float, default=1.0,
                     help="CPU baseline: seconds of BH queries per snapshot (the build is timed apart)")
     ap.add_argument("--locality", action="store_true",
                     help="diagnostic: label-distance histogram of P's edges in the final Morton order (stderr)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:   # a plain run: setup, warmup, the timed steps, --dump-outputs, the line
+        a.trace, a.no_cpu_baseline, a.no_cli_e2e = 0, True, True
+    if a.detail_out is None:
+        a.detail_out = os.path.join(a.dump_dir, "bench_detail.json") if a.full else ""
+    return a
 
 
 def gmm(n, d, seed, device):
@@ -264,8 +288,8 @@ def main():
     n, d, k = a.n, a.dim, a.k
     kk = min(k, n - 1)
     r0, r1 = T.shard_rows(n, world, rank)
+    a.iterations = max(a.iterations, a.steps)   # K > T: K steps of one iteration each
     steps = a.steps if a.steps > 0 else a.iterations
-    steps = min(steps, a.iterations)
 
     # ---------------------------------------------------------- setup stages
     if a.config == "c5":
@@ -291,20 +315,26 @@ def main():
     sync_barrier(world)
     t_setup = max_over_ranks(time.perf_counter() - t0, world)
 
-    # ---------- warmup on a snapshot: the first W steps of the schedule, untimed;
-    # inside it the pre-expansion window t = 1..20 is timed on its own (window_it_s)
+    # ---------- warmup on a snapshot: W steps of the schedule from its first, untimed
+    # (after the K-th step the snapshot is restored and the schedule starts again);
+    # inside its first pass the pre-expansion window t = 1..20 is timed on its own (window_it_s)
     chunks = [(a.iterations * (k - 1) // steps + 1, a.iterations * k // steps) for k in range(1, steps + 1)]
-    w_end = chunks[min(a.warmup, steps) - 1][1] if a.warmup > 0 else 0
     win = min(20, a.iterations)
     t_win = None
-    for t in range(1, w_end + 1):
-        if t == 1:
-            sync_barrier(world)
-            t0 = time.perf_counter()
-        ctx.dev_opt_step(t)
-        if t == win:
-            sync_barrier(world)
-            t_win = max_over_ranks(time.perf_counter() - t0, world)
+    for w in range(a.warmup):
+        c0, c1 = chunks[w % steps]
+        if w > 0 and w % steps == 0:
+            torch.cuda.synchronize()
+            Y.copy_(snap[0]); upd.copy_(snap[1]); gains.copy_(snap[2])
+            ctx.dev_opt_setup(params, orp, oc, ov, n, Y, upd, gains)
+        for t in range(c0, c1 + 1):
+            if t == 1 and w == 0:
+                sync_barrier(world)
+                t0 = time.perf_counter()
+            ctx.dev_opt_step(t)
+            if t == win and w < steps:
+                sync_barrier(world)
+                t_win = max_over_ranks(time.perf_counter() - t0, world)
     torch.cuda.synchronize()
     Y.copy_(snap[0]); upd.copy_(snap[1]); gains.copy_(snap[2])
     ctx.dev_opt_setup(params, orp, oc, ov, n, Y, upd, gains)   # fresh loss slots, kernel logs, labels
@@ -330,6 +360,8 @@ def main():
     t_out = time.perf_counter() - t0
     alog = ctx.dev_opt_attract_log()
     upd_ms = ctx.stage_ms("opt.update")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, Y_final, upd[:n], gains[:n], losses)
 
     # ------- trace pass (untimed): the same schedule again from the same state,
     # profiled every --trace iterations (per-stage times, BH work counters),
@@ -464,7 +496,7 @@ def main():
     # this same command, each file naming the commit it was measured at
     # (profiles/PMC_ATTRACT, profiles/PMC_BH below)
     here = os.path.dirname(os.path.abspath(__file__))
-    if n == 1_000_000 and d == 128 and world == 1 and a.config == "c3":
+    if a.full and n == 1_000_000 and d == 128 and world == 1 and a.config == "c3":
         tf = os.path.join(here, "profiles", PMC_ATTRACT)
         if os.path.exists(tf):
             with open(tf) as fh:
@@ -510,6 +542,28 @@ def main():
     ctx.close()
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(out_dir, Y, upd, gains, losses, budget=60_000_000):
+    """--dump-outputs: what the timed schedule handed back -- the working set
+    tsne_dev_opt_sync wrote to the caller's buffers after its last step (Y,
+    update, gains: float64 [n, C]) and the schedule's losses (iteration, KL) --
+    as <out_dir>/<name>.npy.  Above `budget` bytes the three arrays keep the
+    same seeded sample of rows, whose indices go to rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n, C = Y.shape
+    rows = None
+    if 3 * n * C * 8 > budget:
+        m = budget // (3 * C * 8 + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    for name, arr in (("Y", Y), ("update", upd), ("gains", gains)):
+        arr = arr.cpu().numpy() if isinstance(arr, torch.Tensor) else arr
+        arr = arr if rows is None else arr[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    ts = sorted(losses)
+    np.save(os.path.join(out_dir, "loss_iterations.npy"), np.array(ts, dtype=np.float64))
+    np.save(os.path.join(out_dir, "losses.npy"), np.array([losses[t] for t in ts], dtype=np.float64))
 
 
 def cli_end_to_end(a, X_host, dev):

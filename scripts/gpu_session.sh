@@ -1,6 +1,6 @@
 # GPU session script: STEPS (space-separated) selects what runs, each GPU step
 # under its own time limit, outputs under gpurun_out/r${ROUND:-5}$TAG/:
-#   driver      bench.py exactly as the driver runs it (--gpus 1 --steps 20 --warmup 5, CPU baseline included)
+#   driver      bench.py --full --gpus 1 --steps 20 --warmup 5 (every leg, CPU baseline included)
 #   mksnaps     bench.py --dump-y 250,450,650 into /tmp/snaps (the snapshots the snap steps read)
 #   snap        bh_snap.py on snaps/Y_t{250,450,650}.npy per SNAP_VARS entry ("-" = defaults, else KEY=VALUE;
 #               SNAP_ARGS: more bh_snap arguments, e.g. --stats)
@@ -26,7 +26,7 @@ run() { local lim=$1; shift; timeout -k 10 $lim "$@"; }
 tst() { run "$@"; local rc=$?; echo "tests rc=$rc" >> $O/status.txt; case $rc in 0|1) return 0;; *) return $rc;; esac; }
 has() { [[ " ${STEPS:-} " == *" $1 "* ]]; }
 if has driver; then
-  run 600 python bench.py --gpus 1 --steps 20 --warmup 5 --detail-out $O/bench_detail.json > $O/driver_bench.json 2> $O/driver_bench.err || exit $?
+  run 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail-out $O/bench_detail.json > $O/driver_bench.json 2> $O/driver_bench.err || exit $?
 fi
 if has mksnaps; then
   mkdir -p $SN
@@ -66,7 +66,7 @@ if has bench; then
     case "$v" in -) ;; lib=*) lib="${v#lib=}" ;; *) opt="--option ${v//+/ --option }" ;; esac
     bi=$((${bi:-0}+1))
     echo "# $v" >> $O/bench.jsonl
-    TSNE_HIP_LIB="$lib" run 400 python bench.py --no-cpu-baseline --no-cli-e2e $opt --detail-out $O/bench_detail_$bi.json >> $O/bench.jsonl 2>> $O/bench.err || exit $?
+    TSNE_HIP_LIB="$lib" run 400 python bench.py --full --no-cpu-baseline --no-cli-e2e $opt --detail-out $O/bench_detail_$bi.json >> $O/bench.jsonl 2>> $O/bench.err || exit $?
   done
 fi
 if has tests3d; then
@@ -80,7 +80,7 @@ if has bench4; then
     opt=""; lib=""
     case "$v" in -) ;; lib=*) lib="${v#lib=}" ;; *) opt="--option $v" ;; esac
     echo "# $v" >> $O/bench4.jsonl
-    TSNE_HIP_LIB="$lib" run 600 python bench.py --config c4 --no-cpu-baseline $opt >> $O/bench4.jsonl 2>> $O/bench4.err || exit $?
+    TSNE_HIP_LIB="$lib" run 600 python bench.py --full --config c4 --no-cpu-baseline $opt >> $O/bench4.jsonl 2>> $O/bench4.err || exit $?
   done
 fi
 if has ktrace; then
