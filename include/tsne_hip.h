@@ -209,6 +209,13 @@ int tsne_ctx_synchronize(tsne_ctx *ctx);
  *                             relaxed arrivals ordered by gfx950's in-order
  *                             issue (the same trees; no measurable cost
  *                             difference);
+ *   "build_fuse" 1            the 2-D tree build's short chain: the coherent
+ *                             sort computes the Morton keys itself and writes
+ *                             the sorted positions, the in-root count and the
+ *                             duplicate counts from its bucket workgroups, and
+ *                             the subtree moments run on the second stream
+ *                             beside the traversal; 0: one launch per pass
+ *                             (the same arrays, bit for bit);
  *   "loop_serial" 0           1 (a loopback tsne_ctx_create_multi group, set
  *                             before tsne_optimize): the ranks take turns on the
  *                             device and log their work between collectives --

@@ -33,8 +33,7 @@
 namespace tsne {
 namespace {
 
-constexpr int LEVELS = 31;                 // 62 key bits
-constexpr uint64_t OUT_KEY = 1ull << 63;   // outside the root cell: sorts last
+constexpr uint64_t OUT_KEY = MORTON2_OUT_KEY;      // outside the root cell: sorts last (csort.hpp: 31 levels, 62 key bits)
 constexpr int STACK = 320;                 // batch pops (<= 8 cells) while <= STACK/2 entries, then
                                            // depth-first (+3 per level, <= 35 levels): never overflows
 constexpr int QREC_V4 = sizeof(QRec) / 16; // 16-byte pieces of a record
@@ -93,7 +92,7 @@ __global__ void bbox_partial(const double *__restrict__ Y, int64_t n, double *__
 // moments would serve (mom_flag[1] >= mom_flag[2]), then mom_flag[1] restarts.
 __global__ void bbox_final(const double *__restrict__ part, int nb, double *__restrict__ W,
                            int32_t *__restrict__ meta, double *__restrict__ bb, int32_t *__restrict__ mom_flag,
-                           int32_t *__restrict__ mom_items) {
+                           int32_t *__restrict__ mom_items, int32_t *__restrict__ dflag) {
     __shared__ double sm[4][4];
     double mnx = __builtin_inf(), mxx = -__builtin_inf(), mny = __builtin_inf(), mxy = -__builtin_inf();
     for (int b = threadIdx.x; b < nb; b += blockDim.x) {
@@ -120,30 +119,11 @@ __global__ void bbox_final(const double *__restrict__ part, int nb, double *__re
             mom_flag[1] = 0;
         }
         if (mom_items) *mom_items = 0;
+        if (dflag) *dflag = 0;   // (Options::build_fuse: the build's duplicate flag cleared here, not by a fill)
     }
 }
 
-// Morton key by replaying the reference cell arithmetic (no FMA contraction).
-// Fast path: away from cell boundaries the replay's digits are those of the
-// exact quantisation X = (p + W) / (2W) * 2^31 (every coarser boundary is
-// also a level-31 boundary, and the reference's rounded cell centres sit
-// within a few ulps of the exact ones), so a point whose fixed-point
-// coordinates are more than 1e-4 of a level-31 cell away from every boundary
-// takes the quantised digits; the rest (a fraction ~4e-4) and every
-// out-of-range case replay the reference arithmetic.
-__device__ __forceinline__ bool quant_digits(double p, double W, uint32_t &q) {
-    const double t = (p + W) / (2.0 * W) * 2147483648.0;   // in [0, 2^31] for in-root points
-    if (!(t >= 0.0 && t < 2147483648.0)) return false;
-    const double f = floor(t);
-    const double fr = t - f;
-    // t carries <= ~3 ulp(2^31) = 1.4e-6 of rounding, the reference's cell
-    // centres <= 31 roundings = 7.4e-6 (both in level-31 cell units): a band
-    // of 1e-4 is far outside both
-    if (fr < 1e-4 || fr > 1.0 - 1e-4) return false;          // near a boundary: replay
-    q = (uint32_t)f;
-    return true;
-}
-
+// (the Morton key itself: morton2_key, csort.hpp -- shared with the fused sort front end)
 __global__ void morton_keys(const double *__restrict__ Y, int64_t n, const double *__restrict__ Wp,
                             uint64_t *__restrict__ keys, int32_t *__restrict__ idx,
                             int32_t *__restrict__ meta) {
@@ -151,44 +131,7 @@ __global__ void morton_keys(const double *__restrict__ Y, int64_t n, const doubl
     const bool live = i0 < n;
     const int64_t i = live ? i0 : n - 1;
     const double W = *Wp;
-    const double px = Y[2 * i], py = Y[2 * i + 1];
-    double x = 0.0, y = 0.0, hw = W, hh = W;
-    bool in = live && (__dsub_rn(x, hw) <= px) && (__dadd_rn(x, hw) >= px) && (__dsub_rn(y, hh) <= py) &&
-              (__dadd_rn(y, hh) >= py);
-    uint64_t key = 0;
-    uint32_t qx, qy;
-    if (in && W > 0.0 && quant_digits(px, W, qx) && quant_digits(py, W, qy)) {
-        // digit l: (west/east from x, north/south from y): q = 2 * south + east,
-        // south = y below the centre = high bit of qy clear
-        uint64_t k = 0;
-        for (int l = 30; l >= 0; --l) {
-            const uint32_t east = (qx >> l) & 1u, south = 1u - ((qy >> l) & 1u);
-            k = (k << 2) | (uint64_t)(2u * south + east);
-        }
-        key = k;
-    } else if (in) {
-        for (int l = 0; l < LEVELS; ++l) {
-            const double nw = __dmul_rn(0.5, hw), nh = __dmul_rn(0.5, hw);
-            const double xw = __dsub_rn(x, nw), xe = __dadd_rn(x, nw);
-            const double yn = __dadd_rn(y, nh), ys = __dsub_rn(y, nh);
-            const bool inW = (__dsub_rn(xw, nw) <= px) && (__dadd_rn(xw, nw) >= px);
-            const bool inE = (__dsub_rn(xe, nw) <= px) && (__dadd_rn(xe, nw) >= px);
-            const bool inN = (__dsub_rn(yn, nh) <= py) && (__dadd_rn(yn, nh) >= py);
-            const bool inS = (__dsub_rn(ys, nh) <= py) && (__dadd_rn(ys, nh) >= py);
-            int q;
-            if (inN && inW) q = 0;        // NW
-            else if (inN && inE) q = 1;   // NE
-            else if (inS && inW) q = 2;   // SW
-            else q = 3;                   // SE (or a rounding gap: see header)
-            x = (q & 1) ? xe : xw;
-            y = (q & 2) ? ys : yn;
-            hw = nw;
-            hh = nh;
-            key = (key << 2) | (uint64_t)q;
-        }
-    } else {
-        key = OUT_KEY;
-    }
+    const uint64_t key = live ? morton2_key(Y[2 * i], Y[2 * i + 1], W) : MORTON2_OUT_KEY;
     if (live) {
         keys[i] = key;
         idx[i] = (int32_t)i;
@@ -264,9 +207,11 @@ __global__ void karras_build(const uint64_t *__restrict__ k, int64_t n, const in
                              BHNode *__restrict__ nodes, int32_t *__restrict__ parent_leaf,
                              int32_t *__restrict__ parent_node, int32_t *__restrict__ arrive,
                              int32_t *__restrict__ arrive2, int32_t *__restrict__ fstart, int32_t gen,
-                             int32_t *__restrict__ top_cnt) {
+                             int32_t *__restrict__ top_cnt, int32_t *root_ref) {
     const int m = meta[0];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    // (the fused chain: m was summed by the sort's bucket workgroups, the root ref of count_in_root follows here)
+    if (root_ref && i == 0) *root_ref = m >= 2 ? 0 : (m == 1 ? ~0 : INT32_MIN);
     if (i >= m - 1) return;
     if (i == 0 && top_cnt) *top_cnt = 0;
     arrive[i] = 0;
@@ -4007,6 +3952,19 @@ double bh_near_dmax(double theta, double tol) {
     return d;
 }
 
+// moment_count reads the nodes' cnt (after dup_apply's corrections),
+// moment_items their bottom-up boxes: after the whole build, on stream ms
+static void bh_moments(BHTree &t, hipStream_t ms) {
+    const int64_t n = t.n;
+    hipLaunchKernelGGL(moment_count, dim3(ceil_div(n + 1, 1024)), dim3(1024), 0, ms, t.nodes, n, t.meta, t.mom_flag,
+                       t.mom_cnt, t.mom_list, t.meta, t.mom_off, t.mom_item);
+    const int mgrid = (int)std::min<int64_t>(2048, std::max<int64_t>(1, ceil_div(n, 256)));
+    hipLaunchKernelGGL(moment_items<true>, dim3(mgrid), dim3(256), 0, ms, t.pos, t.nodes, t.mom_off, n, t.mom_item,
+                       t.mom_part, t.mom_cnt, t.mom);
+    hipLaunchKernelGGL(moment_reduce, dim3(mgrid), dim3(256), 0, ms, t.meta, t.mom_list, t.mom_cnt, t.mom_off,
+                       t.mom_part, t.mom);
+}
+
 void bh_build(tsne_ctx *ctx, BHTree &t, const double *dY, double theta, const int32_t *rowmap, bool root_tile_ok,
               double near_tol) {
     if (near_tol < 0.0) near_tol = bh_near_tol(ctx, false);
@@ -4015,10 +3973,12 @@ void bh_build(tsne_ctx *ctx, BHTree &t, const double *dY, double theta, const in
     const int64_t n = t.n;
     t.rowmap = rowmap;
     t.root_tile = false;
-    TSNE_HIP(hipMemsetAsync(t.dflag, 0, sizeof(int32_t), st));
+    t.mom_deferred = false;
+    const bool fuse_opt = ctx->opts.build_fuse != 0;
+    if (!fuse_opt) TSNE_HIP(hipMemsetAsync(t.dflag, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(bbox_partial, dim3(t.bbox_blocks), dim3(256), 0, st, dY, n, t.bbox_part);
     hipLaunchKernelGGL(bbox_final, dim3(1), dim3(256), 0, st, t.bbox_part, t.bbox_blocks, t.W, t.meta, t.bb,
-                       t.mom_flag, t.mom_off + n);
+                       t.mom_flag, t.mom_off + n, fuse_opt ? t.dflag : nullptr);
     // once the box failed the root-tile test by 2^k (k >= 3), the next 4 (k - 2)
     // builds (<= 64) skip the test and its host read-back: the embedding
     // shrinks by a few % per iteration at most (C3: extent 1e-3 -> 9e-5 over
@@ -4068,24 +4028,34 @@ void bh_build(tsne_ctx *ctx, BHTree &t, const double *dY, double theta, const in
         }
         TSNE_HIP(hipMemsetAsync(t.dflag, 0, sizeof(int32_t), st));   // dup_count recomputes it
     }
-    hipLaunchKernelGGL(morton_keys, dim3(ceil_div(n, 256)), dim3(256), 0, st, dY, n, t.W, t.keys, t.idx, t.meta);
-    TSNE_LAUNCH_CHECK();
+    // Options::build_fuse on the coherent-sort path: the sort's own kernels compute the
+    // keys and write what count_in_root, gather_sorted and dup_count write (csort.hpp)
+    const bool csort = t.cs.P > 0 && t.cs_primed && ctx->opts.coherent_sort;
+    const bool fuse = csort && ctx->opts.build_fuse;
+    if (!fuse) {
+        hipLaunchKernelGGL(morton_keys, dim3(ceil_div(n, 256)), dim3(256), 0, st, dY, n, t.W, t.keys, t.idx, t.meta);
+        TSNE_LAUNCH_CHECK();
+    }
     // the previous full build's order buckets the keys (csort.hpp); the first
     // build, small trees and Options::coherent_sort = 0: rocPRIM's sort (the same
     // result: keys ascending, ties by point index)
-    if (t.cs.P > 0 && t.cs_primed && ctx->opts.coherent_sort) {
+    if (fuse) {
+        csort_run_fused2(ctx, t.cs, dY, t.W, t.idx_sorted, t.keys_sorted, t.idx_sorted,
+                         Csort2Out{t.pos, t.inv, t.meta, t.dupc, t.vid, t.dflag}, st);
+    } else if (csort) {
         csort_run(ctx, t.cs, t.keys, t.idx_sorted, t.keys_sorted, t.idx_sorted, st);
     } else {
         size_t tb = t.sort_tmp_bytes;
         morton_sort(t.sort_tmp, tb, t.keys, t.keys_sorted, t.idx, t.idx_sorted, n, st);
     }
     t.cs_primed = true;
-    hipLaunchKernelGGL(count_in_root, dim3(1), dim3(64), 0, st, t.keys_sorted, n, t.meta);
+    if (!fuse) hipLaunchKernelGGL(count_in_root, dim3(1), dim3(64), 0, st, t.keys_sorted, n, t.meta);
     // (trav_front_cur: predictions from the previous traversal's per-point costs,
     // the order made on the second stream while the build goes on)
     const bool cur_order = ctx->opts.trav_front_cur > 0.0 && t.pcost_valid && t.sel_waves == ceil_div(n, 64);
-    hipLaunchKernelGGL(gather_sorted, dim3(ceil_div(n, 256)), dim3(256), 0, st, dY, t.idx_sorted, n, t.pos, t.inv,
-                       cur_order ? t.pcost : nullptr, cur_order ? t.pred : nullptr);
+    if (!fuse || cur_order)   // (fused: only for the predictions)
+        hipLaunchKernelGGL(gather_sorted, dim3(ceil_div(n, 256)), dim3(256), 0, st, dY, t.idx_sorted, n, t.pos, t.inv,
+                           cur_order ? t.pcost : nullptr, cur_order ? t.pred : nullptr);
     t.order_ready = false;
     if (cur_order) {
         TSNE_HIP(hipEventRecord(ctx->aux_ev[0], st));
@@ -4096,14 +4066,16 @@ void bh_build(tsne_ctx *ctx, BHTree &t, const double *dY, double theta, const in
         TSNE_HIP(hipEventRecord(t.ord_ev, ctx->aux_stream));
         t.order_ready = true;
     }
-    hipLaunchKernelGGL(dup_count, dim3(ceil_div(n, 256)), dim3(256), 0, st, t.pos, t.keys_sorted, n, t.dupc, t.vid,
-                       t.dflag);
+    if (!fuse)
+        hipLaunchKernelGGL(dup_count, dim3(ceil_div(n, 256)), dim3(256), 0, st, t.pos, t.keys_sorted, n, t.dupc, t.vid,
+                           t.dflag);
     if (++t.gen <= 0) {   // wrapped: clear the marks once
         TSNE_HIP(hipMemsetAsync(t.fstart, 0, sizeof(int32_t) * n, st));
         t.gen = 1;
     }
     hipLaunchKernelGGL(karras_build, dim3(ceil_div(n, 256)), dim3(256), 0, st, t.keys_sorted, n, t.meta,
-                       t.nodes, t.parent_leaf, t.parent_node, t.arrive, t.arrive2, t.fstart, t.gen, t.top_cnt);
+                       t.nodes, t.parent_leaf, t.parent_node, t.arrive, t.arrive2, t.fstart, t.gen, t.top_cnt,
+                       fuse ? t.meta + 1 : nullptr);
     const double inv_theta = theta > 0.0 ? 1.0 / theta : __builtin_inf();
     hipLaunchKernelGGL(bottom_up_intra, dim3(ceil_div(n, BU_NB)), dim3(BU_NB), 0, st, t.pos, t.meta, t.W, inv_theta,
                        t.nodes, t.agg, t.parent_leaf, t.parent_node, t.fstart, t.gen, t.top_list, t.top_cnt);
@@ -4123,14 +4095,14 @@ void bh_build(tsne_ctx *ctx, BHTree &t, const double *dY, double theta, const in
     const DupView dv{t.tiecnt, t.notile, t.vflag, t.vcntf, t.vcom, (int32_t)n};
     hipLaunchKernelGGL(build_qrec, dim3(ceil_div(n, 256)), dim3(256), 0, st, t.nodes, t.pos, t.meta, inv_theta,
                        t.near_dmax, t.dflag, dv, t.qrec);
-    // subtree moments for the all-open fast path
-    hipLaunchKernelGGL(moment_count, dim3(ceil_div(n + 1, 1024)), dim3(1024), 0, st, t.nodes, n, t.meta, t.mom_flag,
-                       t.mom_cnt, t.mom_list, t.meta, t.mom_off, t.mom_item);
-    const int mgrid = (int)std::min<int64_t>(2048, std::max<int64_t>(1, ceil_div(n, 256)));
-    hipLaunchKernelGGL(moment_items<true>, dim3(mgrid), dim3(256), 0, st, t.pos, t.nodes, t.mom_off, n, t.mom_item,
-                       t.mom_part, t.mom_cnt, t.mom);
-    hipLaunchKernelGGL(moment_reduce, dim3(mgrid), dim3(256), 0, st, t.meta, t.mom_list, t.mom_cnt, t.mom_off,
-                       t.mom_part, t.mom);
+    // subtree moments for the all-open fast path.  The traversal only records
+    // which moments a query wants; their values are read by the kernels after it
+    // (tile_apply, moment_apply, narrow_moment_apply).  With Options::build_fuse
+    // the three kernels therefore leave the chain in front of the traversal:
+    // bh_repulsion launches them on the second stream once the traversal is
+    // enqueued, and joins before the first reader.
+    t.mom_deferred = ctx->opts.build_fuse && ctx->aux_stream;
+    if (!t.mom_deferred) bh_moments(t, st);
     TSNE_LAUNCH_CHECK();
 }
 
@@ -4219,6 +4191,20 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
         }
     }
     t.ran_stream = stream;
+    // the moments the build deferred (Options::build_fuse): the streaming
+    // consumers read them beside the traversal, so there they go first; else on
+    // the second stream behind the narrow waves, enqueued after the traversal
+    // (which stays the first launch behind the build), joined before tile_apply
+    bool mom_late = false;
+    if (t.mom_deferred) {
+        t.mom_deferred = false;
+        if (stream) bh_moments(t, st);
+        else mom_late = true;
+    }
+    if (mom_late && !narrow) {   // (narrow: its own event below orders the second stream behind the build)
+        TSNE_HIP(hipEventRecord(ctx->aux_ev[0], st));
+        TSNE_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_ev[0], 0));
+    }
     stv.prio = o.trav_prio;   // (also without streaming)
     if (o.trav_front > 0.0 && narrow && t.front_waves == waves) stv.border = t.trav_order;
     if (t.order_ready && narrow && !plim && !qlist && s0 == 0 && waves == ceil_div(t.n, 64)) {
@@ -4239,6 +4225,11 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
     hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64 * TRAV_WPB), 0, st, t.pos, t.dupc, t.nodes, t.qrec, t.ttask, t.ttask_n,
                        t.meta, t.mom_flag, mom_tol, theta, s0, s1, qlist, (int32_t)t.n, dF, dz, visits, bcost, t.wcost,
                        t.tcost, clab, nv, plim, sv, stv);
+    if (mom_late) {
+        bh_moments(t, ctx->aux_stream);
+        if (!t.mom_ev) TSNE_HIP(hipEventCreateWithFlags(&t.mom_ev, hipEventDisableTiming));
+        TSNE_HIP(hipEventRecord(t.mom_ev, ctx->aux_stream));
+    }
     if (stream) {   // the consumers beside the traversal, then their moments and sums into F, Z
         // (tile_stream_gate: dispatched once every traversal block has started,
         // so that they take the slots its tail frees, not slots its blocks need)
@@ -4297,6 +4288,7 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
     }
     cv.slot_w = t.ch_slot_w; cv.slot_c = t.ch_slot_c; cv.nslots = t.ch_nslots;
     cv.Fp = t.ch_Fp; cv.Zp = t.ch_Zp;
+    if (mom_late) TSNE_HIP(hipStreamWaitEvent(st, t.mom_ev, 0));   // t.mom: read from here on
     hipLaunchKernelGGL(tile_apply<0>, dim3(ceil_div(tslots, 4)), dim3(256), 0, st, t.pos, t.nodes, t.ttask,
                        t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.mtask, t.mtask_n, dF, dz, visits, torder, cv,
                        t.mom, SpillView(), stv, t.tcost);

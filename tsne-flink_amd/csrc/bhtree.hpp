@@ -208,6 +208,10 @@ struct BHTree {
     int32_t *pcost = nullptr, *pred = nullptr;
     bool pcost_valid = false, order_ready = false;
     hipEvent_t ord_ev = nullptr;
+    // Options::build_fuse: the build left the subtree moments to the traversal
+    // call (bh_repulsion runs them on the second stream beside the traversal)
+    bool mom_deferred = false;
+    hipEvent_t mom_ev = nullptr;
     bool ran_stream = false;              // the last traversal streamed its lists
     std::string pre;                      // the workspace prefix of this tree's buffers
 };

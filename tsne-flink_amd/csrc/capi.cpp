@@ -153,6 +153,7 @@ static const OptionField k_options[] = {
     {"loop_serial", nullptr, &Options::loop_serial, 0, 1},
     {"bu_acqrel", nullptr, &Options::bu_acqrel, 0, 1},
     {"bh_split", nullptr, &Options::bh_split, 0, 1},
+    {"build_fuse", nullptr, &Options::build_fuse, 0, 1},
 };
 static const OptionField &option_field(const char *key) {
     for (const OptionField &f : k_options)

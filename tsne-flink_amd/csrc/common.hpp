@@ -170,6 +170,9 @@ struct Options {
     double near_tol3_early = 1e-7, near_tol3_late = 5e-6;  // the 3-D octree's
     double mom3_tol = 1e-12;
     int oct_moments = 1;      // 3-D subtree moments
+    int build_fuse = 1;       // 2-D tree build: the fused chain (the sort front end computes the keys and writes pos /
+                              // inv / the in-root count / the duplicate counts itself, csort_run_fused2; the subtree
+                              // moments on the second stream beside the traversal); 0: one launch per pass (same arrays)
     int coherent_sort = 1;    // the trees' Morton sort from the previous build's order (csort.hpp; 0: rocPRIM's radix sort)
     double oct_layout_switch = 6.0;   // 3-D: the 8-query layout while the root half-width < this x sqrt(near_dmax)
     int oct_records = 2;      // 3-D: octal records + the 64-query record traversal (1: the 8-query one; 0: the binary-node walk)

@@ -97,7 +97,11 @@ constexpr int CS_RUNS = 8;
 constexpr int CS_RUN = CS_OVS * CS_PMAX / CS_RUNS;   // 512 samples per run at most
 constexpr int CS_RANK_T = 256;
 
+// (K2: the fused 2-D chain -- no key array yet, a sample's key is computed here)
+template <bool K2>
 __global__ __launch_bounds__(CS_RUN / 2) void cs_split_runs(const uint64_t *__restrict__ keys,
+                                                            const double2 *__restrict__ Y2,
+                                                            const double *__restrict__ Wp,
                                                             const int32_t *__restrict__ prev, int64_t n, int32_t P,
                                                             uint64_t *__restrict__ runs) {
     __shared__ uint64_t s[CS_RUN];
@@ -114,15 +118,26 @@ __global__ __launch_bounds__(CS_RUN / 2) void cs_split_runs(const uint64_t *__re
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         const int i = threadIdx.x + (CS_RUN / 2) * e;
-        if (i < N) s[i] = i < m ? keys[pi[e]] : ~0ull;
+        uint64_t k = ~0ull;
+        if (i < m) {
+            if (K2) {
+                const double2 q = Y2[pi[e]];
+                k = morton2_key(q.x, q.y, *Wp);
+            } else {
+                k = keys[pi[e]];
+            }
+        }
+        if (i < N) s[i] = k;
     }
     __syncthreads();
     bitonic_k<CS_RUN / 2>(s, N);
     for (int i = threadIdx.x; i < m; i += CS_RUN / 2) runs[blockIdx.x * CS_RUN + i] = s[i];
 }
 
+// (zcnt / zcur, the fused chain: the P bucket counts and cursors zeroed here -- the grid has >= P threads)
 __global__ __launch_bounds__(CS_RANK_T) void cs_split_rank(const uint64_t *__restrict__ runs, int32_t P,
-                                                           uint64_t *__restrict__ split) {
+                                                           uint64_t *__restrict__ split, int32_t *__restrict__ zcnt,
+                                                           int32_t *__restrict__ zcur) {
     __shared__ uint64_t s[CS_RUNS * CS_RUN];
     const int S = CS_OVS * P, L = (S + CS_RUNS - 1) / CS_RUNS;
     for (int i = threadIdx.x; i < CS_RUNS * CS_RUN; i += CS_RANK_T) {
@@ -131,6 +146,10 @@ __global__ __launch_bounds__(CS_RANK_T) void cs_split_rank(const uint64_t *__res
     }
     __syncthreads();
     const int j = blockIdx.x * CS_RANK_T + threadIdx.x;
+    if (zcnt && j < P) {
+        zcnt[j] = 0;
+        zcur[j] = 0;
+    }
     if (j >= S) return;
     const int r = j / L, i = j - r * L;
     const uint64_t x = s[r * CS_RUN + i];
@@ -163,15 +182,26 @@ __device__ __forceinline__ int cs_find(const uint64_t *__restrict__ split, int32
     return lo;
 }
 
-__global__ __launch_bounds__(CS_BLK) void cs_count(const uint64_t *__restrict__ keys, const int32_t *__restrict__ prev,
+// (K2: the key of Y[prev[j]] computed here and staged in kst[j], in the previous order, for cs_scatter_scan)
+template <bool K2>
+__global__ __launch_bounds__(CS_BLK) void cs_count(const uint64_t *__restrict__ keys, const double2 *__restrict__ Y2,
+                                                   const double *__restrict__ Wp, const int32_t *__restrict__ prev,
                                                    int64_t n, int32_t P, const uint64_t *__restrict__ split,
-                                                   int32_t *__restrict__ bkt, int32_t *__restrict__ cnt) {
+                                                   int32_t *__restrict__ bkt, int32_t *__restrict__ cnt,
+                                                   uint64_t *__restrict__ kst) {
     __shared__ int32_t h[CS_PMAX];
     for (int b = threadIdx.x; b < P; b += CS_BLK) h[b] = 0;
     __syncthreads();
     const int64_t j = (int64_t)blockIdx.x * CS_BLK + threadIdx.x;
     if (j < n) {
-        const uint64_t k = keys[prev[j]];
+        uint64_t k;
+        if (K2) {
+            const double2 q = Y2[prev[j]];
+            k = morton2_key(q.x, q.y, *Wp);
+            kst[j] = k;
+        } else {
+            k = keys[prev[j]];
+        }
         const int b = cs_find(split, P, k, (int)(j * P / n));
         bkt[j] = b;
         atomicAdd(&h[b], 1);
@@ -243,13 +273,99 @@ __global__ __launch_bounds__(CS_BLK) void cs_scatter(const uint64_t *__restrict_
     }
 }
 
+// The fused chain's scatter: cs_scan folded in.  Every workgroup scans the
+// P <= CS_BLK bucket counts itself (one per thread: a wave scan and the 16
+// wave sums), so a bucket's base is off[c] + the cursor's atomic (cur zeroed
+// by cs_split_rank); the keys come from cs_count's staging array (coalesced)
+// instead of a second gather.  Workgroup 0 writes off[] and the oversize
+// statistics for cs_bucket and the counters, as cs_scan does.
+static_assert(CS_PMAX <= CS_BLK, "one bucket count per thread");
+__global__ __launch_bounds__(CS_BLK) void cs_scatter_scan(const uint64_t *__restrict__ kst,
+                                                          const int32_t *__restrict__ prev, int64_t n, int32_t P,
+                                                          const int32_t *__restrict__ bkt,
+                                                          const int32_t *__restrict__ cnt, int32_t *__restrict__ off,
+                                                          int32_t *__restrict__ cur, int32_t *__restrict__ stat,
+                                                          uint64_t *__restrict__ kb, int32_t *__restrict__ vb) {
+    __shared__ int32_t h[CS_PMAX], base[CS_PMAX], wsum[CS_BLK / 64];
+    __shared__ int32_t nover;
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    h[t] = 0;
+    if (t == 0) nover = 0;
+    const int c = t < P ? cnt[t] : 0;
+    int inc = c;   // inclusive scan over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += v;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int o = inc - c;   // off[t]
+    for (int k = 0; k < w; ++k) o += wsum[k];
+    const int64_t j = (int64_t)blockIdx.x * CS_BLK + t;
+    int b = 0, r = 0;
+    if (j < n) {
+        b = bkt[j];
+        r = atomicAdd(&h[b], 1);   // rank within this workgroup's share of the bucket (any order: sorted below)
+    }
+    __syncthreads();
+    if (t < P && h[t]) base[t] = o + atomicAdd(&cur[t], h[t]);
+    if (blockIdx.x == 0 && t < P) {
+        off[t] = o;
+        if (t == P - 1) off[P] = o + c;
+        if (c > CS_CAP) atomicAdd(&nover, 1);
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && t == 0) { stat[0] = nover; stat[1] += nover; }   // the last sort's, and the running total
+    if (j < n) {
+        const int32_t slot = base[b] + r;
+        kb[slot] = kst[j];
+        vb[slot] = prev[j];
+    }
+}
+
+// The fused chain's epilogue of a sorted bucket (a / v: LDS or the oversized
+// bucket's scratch, m entries at offset o): what gather_sorted, count_in_root
+// and dup_count compute from the sorted arrays.  cs_find sends equal keys to
+// one bucket, so a run of equal keys -- dup_count's search range -- never
+// straddles buckets, and the in-root keys (< MORTON2_OUT_KEY) are a prefix of
+// the bucket: the one thread at its end adds the bucket's share to meta[0].
+template <class KP, class VP>
+__device__ __forceinline__ void cs_bucket_out(KP a, VP v, int m, int o, const double2 *__restrict__ Y2,
+                                              const Csort2Out &out) {
+    for (int i = threadIdx.x; i < m; i += CS_SORT_T) {
+        const uint64_t k = a[i];
+        const int32_t p = v[i];
+        const double2 q = Y2[p];
+        out.pos[o + i] = q;
+        out.inv[p] = o + i;
+        if (k < MORTON2_OUT_KEY && (i == m - 1 || a[i + 1] >= MORTON2_OUT_KEY)) atomicAdd(&out.meta[0], i + 1);
+        int32_t c = 1;
+        int first = i;   // value id: the first sorted position holding this exact point
+        for (int s = i - 1; s >= 0 && a[s] == k; --s) {
+            const double2 u = Y2[v[s]];
+            if (u.x == q.x && u.y == q.y) { ++c; first = s; }
+        }
+        for (int s = i + 1; s < m && a[s] == k; ++s) {
+            const double2 u = Y2[v[s]];
+            c += (u.x == q.x && u.y == q.y);
+        }
+        out.dupc[o + i] = c;
+        out.vid[o + i] = o + first;
+        if (c > 1) out.dflag[0] = 1;
+    }
+}
+
 // One workgroup per bucket: its (key, point) pairs sorted and written to the
 // output at the bucket's offset.  Over CS_CAP: the same bitonic network in
 // the bucket's private scratch (kb / vb + n + 2 off: disjoint, N <= 2 m).
+// (EPI: the fused 2-D chain's epilogue, cs_bucket_out)
+template <bool EPI>
 __global__ __launch_bounds__(CS_SORT_T) void cs_bucket(const int32_t *__restrict__ cnt, const int32_t *__restrict__ off,
                                                        int64_t n, uint64_t *kb, int32_t *vb,
                                                        uint64_t *__restrict__ keys_sorted,
-                                                       int32_t *__restrict__ idx_sorted) {
+                                                       int32_t *__restrict__ idx_sorted,
+                                                       const double2 *__restrict__ Y2, const Csort2Out out) {
     __shared__ uint64_t sk[CS_CAP];
     __shared__ int32_t sv[CS_CAP];
     const int b = blockIdx.x;
@@ -268,6 +384,7 @@ __global__ __launch_bounds__(CS_SORT_T) void cs_bucket(const int32_t *__restrict
             keys_sorted[o + i] = sk[i];
             idx_sorted[o + i] = sv[i];
         }
+        if (EPI) cs_bucket_out(sk, sv, m, o, Y2, out);
     } else {
         uint64_t *a = kb + n + 2 * (int64_t)o;
         int32_t *v = vb + n + 2 * (int64_t)o;
@@ -281,6 +398,7 @@ __global__ __launch_bounds__(CS_SORT_T) void cs_bucket(const int32_t *__restrict
             keys_sorted[o + i] = a[i];
             idx_sorted[o + i] = v[i];
         }
+        if (EPI) cs_bucket_out(a, v, m, o, Y2, out);
     }
 }
 
@@ -301,6 +419,7 @@ void csort_alloc(tsne_ctx *ctx, CoherentSort &cs, int64_t n, const std::string &
     cs.kb = ws.get<uint64_t>(pre + "cs.kb", 3 * (size_t)n);
     cs.vb = ws.get<int32_t>(pre + "cs.vb", 3 * (size_t)n);
     cs.stat = ws.get<int32_t>(pre + "cs.stat", 2);
+    cs.kst = ws.get<uint64_t>(pre + "cs.kst", n);
     TSNE_HIP(hipMemsetAsync(cs.stat, 0, 2 * sizeof(int32_t), ctx->stream));
 }
 
@@ -318,15 +437,37 @@ void csort_run(tsne_ctx *ctx, CoherentSort &cs, const uint64_t *keys, const int3
     TSNE_REQUIRE(cs.P > 0, "coherent sort not allocated");
     const int64_t n = cs.n;
     const int64_t nb = ceil_div(n, CS_BLK);
-    hipLaunchKernelGGL(cs_split_runs, dim3(CS_RUNS), dim3(CS_RUN / 2), 0, st, keys, prev, n, cs.P, cs.runs);
+    hipLaunchKernelGGL(cs_split_runs<false>, dim3(CS_RUNS), dim3(CS_RUN / 2), 0, st, keys, nullptr, nullptr, prev, n,
+                       cs.P, cs.runs);
     hipLaunchKernelGGL(cs_split_rank, dim3(ceil_div(CS_OVS * cs.P, CS_RANK_T)), dim3(CS_RANK_T), 0, st, cs.runs, cs.P,
-                       cs.split);
+                       cs.split, nullptr, nullptr);
     TSNE_HIP(hipMemsetAsync(cs.cnt, 0, sizeof(int32_t) * cs.P, st));
-    hipLaunchKernelGGL(cs_count, dim3(nb), dim3(CS_BLK), 0, st, keys, prev, n, cs.P, cs.split, cs.bkt, cs.cnt);
+    hipLaunchKernelGGL(cs_count<false>, dim3(nb), dim3(CS_BLK), 0, st, keys, nullptr, nullptr, prev, n, cs.P, cs.split,
+                       cs.bkt, cs.cnt, nullptr);
     hipLaunchKernelGGL(cs_scan, dim3(1), dim3(1024), 0, st, cs.cnt, cs.P, cs.off, cs.cur, cs.stat);
     hipLaunchKernelGGL(cs_scatter, dim3(nb), dim3(CS_BLK), 0, st, keys, prev, n, cs.P, cs.bkt, cs.cur, cs.kb, cs.vb);
-    hipLaunchKernelGGL(cs_bucket, dim3(cs.P), dim3(CS_SORT_T), 0, st, cs.cnt, cs.off, n, cs.kb, cs.vb, keys_sorted,
-                       idx_sorted);
+    hipLaunchKernelGGL(cs_bucket<false>, dim3(cs.P), dim3(CS_SORT_T), 0, st, cs.cnt, cs.off, n, cs.kb, cs.vb,
+                       keys_sorted, idx_sorted, nullptr, Csort2Out{});
+    TSNE_LAUNCH_CHECK();
+}
+
+void csort_run_fused2(tsne_ctx *ctx, CoherentSort &cs, const double *Y, const double *W, const int32_t *prev,
+                      uint64_t *keys_sorted, int32_t *idx_sorted, const Csort2Out &out, hipStream_t st) {
+    (void)ctx;
+    TSNE_REQUIRE(cs.P > 0, "coherent sort not allocated");
+    const int64_t n = cs.n;
+    const int64_t nb = ceil_div(n, CS_BLK);
+    const auto Y2 = reinterpret_cast<const double2 *>(Y);
+    hipLaunchKernelGGL(cs_split_runs<true>, dim3(CS_RUNS), dim3(CS_RUN / 2), 0, st, nullptr, Y2, W, prev, n, cs.P,
+                       cs.runs);
+    hipLaunchKernelGGL(cs_split_rank, dim3(ceil_div(CS_OVS * cs.P, CS_RANK_T)), dim3(CS_RANK_T), 0, st, cs.runs, cs.P,
+                       cs.split, cs.cnt, cs.cur);
+    hipLaunchKernelGGL(cs_count<true>, dim3(nb), dim3(CS_BLK), 0, st, nullptr, Y2, W, prev, n, cs.P, cs.split, cs.bkt,
+                       cs.cnt, cs.kst);
+    hipLaunchKernelGGL(cs_scatter_scan, dim3(nb), dim3(CS_BLK), 0, st, cs.kst, prev, n, cs.P, cs.bkt, cs.cnt, cs.off,
+                       cs.cur, cs.stat, cs.kb, cs.vb);
+    hipLaunchKernelGGL(cs_bucket<true>, dim3(cs.P), dim3(CS_SORT_T), 0, st, cs.cnt, cs.off, n, cs.kb, cs.vb,
+                       keys_sorted, idx_sorted, Y2, out);
     TSNE_LAUNCH_CHECK();
 }
 
