@@ -216,7 +216,14 @@ int tsne_ctx_synchronize(tsne_ctx *ctx);
  *                             the subtree moments run on the second stream
  *                             beside the traversal; 0: one launch per pass
  *                             (the same arrays, bit for bit);
- *   "loop_serial" 0           1 (a loopback tsne_ctx_create_multi group, set
+ *   "transform_resort" 10     tsne_dev_transform_step: the new points are sorted
+ *                             again by the map tree's Morton key every this
+ *                             many steps (0: only at setup); changes no result,
+ *                             only which points share a wave;
+ *   "transform_split" 0       1: a transform step as two launches (the walk,
+ *                             then attraction + update) instead of the fused
+ *                             one; the same bits (an A/B);
+ *   "loop_serial" 0          1 (a loopback tsne_ctx_create_multi group, set
  *                             before tsne_optimize): the ranks take turns on the
  *                             device and log their work between collectives --
  *                             a one-GPU projection of N GPUs, read with
@@ -469,6 +476,72 @@ int tsne_dev_opt_attract_log(tsne_ctx *ctx, int32_t *iters, int32_t *standalone,
  * "opt.attract" (see above), "opt.update" (combine + updateEmbedding +
  * centerEmbedding + write-back, per iteration).  *count = intervals. */
 int tsne_ctx_stage_ms(tsne_ctx *ctx, const char *stage, double *ms_out, int32_t cap, int32_t *count);
+
+/* ------------------------------------- embedding new points into a fitted map */
+/* The reference embedding Yref (n x 2) stays fixed; m new points are placed
+ * into it.  Not in the reference job (which only fits): the pieces are the
+ * reference's own operators applied across two point sets.  2-D only.  On a
+ * tsne_ctx_create_multi handle these run on the first device. */
+
+/* Cross kNN: for each of the m rows of Xq (m x d) the min(k, n) nearest rows
+ * of X (n x d), ascending by (exact fp64 breeze metric, j).  No candidate is
+ * excluded: a query equal to a reference row gets it at distance 0.  Ids and
+ * distances are as exact as tsne_knn's.  idx_out / dist_out: m x min(k, n).
+ * (X and Xq are stacked in a workspace copy: (n + m) x d doubles.) */
+int tsne_knn_cross(tsne_ctx *ctx, const double *X, int64_t n, const double *Xq, int64_t m, int32_t d,
+                   int32_t metric, int32_t k, int32_t *idx_out, double *dist_out);
+int tsne_dev_knn_cross(tsne_ctx *ctx, const double *dX, int64_t n, const double *dXq, int64_t m, int32_t d,
+                       int32_t metric, int32_t k, int32_t *d_idx, double *d_dist);
+
+/* QuadTree.computeRepulsiveForce (QuadTree.scala:123-152) of the tree of the
+ * n points of Y (built as in TsneHelpers.scala:227-256) for m points Q (m x 2)
+ * that are NOT in the tree: F_out (m x 2) and z_out (m), in the order of Q.
+ * The root cell goes through the h / D < theta test like any cell; a leaf
+ * whose point equals the query contributes 0.  Every cell decision is the
+ * reference's (no near-exact or moment shortcuts).  A query's result does not
+ * depend on the other queries of the call, bit for bit. */
+int tsne_repulsion_queries(tsne_ctx *ctx, const double *Y, int64_t n, double theta, const double *Q, int64_t m,
+                           double *F_out, double *z_out);
+int tsne_dev_repulsion_queries(tsne_ctx *ctx, const double *dY, int64_t n, double theta, const double *dQ,
+                               int64_t m, double *d_F, double *d_z);
+
+/* Initial positions of the new points: y_i = sum_e P_e Yref[col_e] over the
+ * point's CSR row (row_ptr[m + 1], col = ids into the reference, P = the
+ * conditional p_{j|i} of tsne_pairwise_affinities on the cross-kNN distances:
+ * row-normalised, not symmetrised), summed sequentially in CSR order.  A row
+ * without entries is TSNE_ERR_ARG.  Y_out: m x 2. */
+int tsne_transform_init(tsne_ctx *ctx, const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m,
+                        const double *Yref, int64_t n, double *Y_out);
+
+/* The transform optimizer: params->iterations iterations that move only the
+ * new points.  Per iteration and new point i, independently of every other:
+ *   rep_i, z_i = computeRepulsiveForce(y_i) over the tree of Yref,
+ *   attr_i     = sum_e (ex P_e) q_e (y_i - Yref[col_e]),  q_e = 1 / (1 + |y_i - Yref[col_e]|^2),
+ *   grad_i     = attr_i - rep_i / z_i      (the point's own normaliser, not a global Z),
+ *   updateEmbedding(grad_i) with params' learning_rate, momenta and min_gain; no centring.
+ * The exaggeration / momentum schedule is tsne_optimize's.  (t, loss) for
+ * t % 10 == 0, loss = sum_i sum_e pe ln(pe / (q_e / z_i)), pe = ex P_e.  With
+ * the per-point z_i a new point's result does not depend on which other
+ * points are in the batch, bit for bit.  Y, upd, gains: m x 2, read and
+ * written back.  m = 0 is a no-op; n_components != 2 is TSNE_ERR_UNSUPPORTED.
+ * The host form validates row_ptr and col (TSNE_ERR_ARG). */
+int tsne_transform(tsne_ctx *ctx, const tsne_params *params, const double *Yref, int64_t n,
+                   const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m, double *Y, double *upd,
+                   double *gains, int32_t *loss_keys, double *loss_vals, int32_t loss_cap, int32_t *n_loss);
+/* Device-resident form.  setup builds the tree of d_Yref once and sorts the
+ * new points by its Morton key; the caller's buffers (all on the device) are
+ * used in place and must stay valid and unchanged by others until the last
+ * step.  step runs iteration t (1-based): one kernel launch, plus a small
+ * reduce on loss iterations.  sync waits for the steps enqueued so far: the
+ * working set is then current in d_Y, d_upd and d_gains (caller's order).
+ * The state may coexist with tsne_dev_opt_*'s. */
+int tsne_dev_transform_setup(tsne_ctx *ctx, const tsne_params *params, const double *d_Yref, int64_t n,
+                             const int64_t *d_row_ptr, const int32_t *d_col, const double *d_P, int64_t m,
+                             double *d_Y, double *d_upd, double *d_gains);
+int tsne_dev_transform_step(tsne_ctx *ctx, int32_t t);
+int tsne_dev_transform_sync(tsne_ctx *ctx);
+int tsne_dev_transform_losses(tsne_ctx *ctx, int32_t *loss_keys, double *loss_vals, int32_t cap,
+                              int32_t *n_loss);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@
 
 #include "bhtree.hpp"
 #include "common.hpp"
+#include "transform.hpp"
 
 namespace tsne {
 
@@ -154,6 +155,8 @@ static const OptionField k_options[] = {
     {"bu_acqrel", nullptr, &Options::bu_acqrel, 0, 1},
     {"bh_split", nullptr, &Options::bh_split, 0, 1},
     {"build_fuse", nullptr, &Options::build_fuse, 0, 1},
+    {"transform_resort", nullptr, &Options::transform_resort, 0, 1 << 30},
+    {"transform_split", nullptr, &Options::transform_split, 0, 1},
 };
 static const OptionField &option_field(const char *key) {
     for (const OptionField &f : k_options)
@@ -348,6 +351,7 @@ int tsne_ctx_destroy(tsne_ctx *ctx) {
         DeviceGuard g(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
         opt_destroy(ctx);
+        transform_destroy(ctx);
         delete ctx->single_tree;
         ctx->single_tree = nullptr;
         comm_destroy(ctx);
@@ -945,6 +949,181 @@ int tsne_dev_opt_sync(tsne_ctx *ctx) {
         ctx = opt_ctx(ctx);
         DeviceGuard g(ctx->device);
         opt_sync(ctx);
+    });
+}
+
+// ------------------------------------------- embedding new points (transform)
+
+// CSR rows of the new points over the reference map: row pointers from 0 and
+// ascending, every column in [0, n) (host entry points; the device API trusts them)
+static void check_cross_csr(const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m, int64_t n,
+                            bool rows_nonempty) {
+    TSNE_REQUIRE(row_ptr != nullptr && row_ptr[0] == 0, "row_ptr[0] must be 0");
+    for (int64_t i = 0; i < m; ++i) {
+        if (row_ptr[i + 1] < row_ptr[i]) fail(TSNE_ERR_ARG, "row_ptr must be ascending");
+        if (rows_nonempty && row_ptr[i + 1] == row_ptr[i])
+            fail(TSNE_ERR_ARG, "row " + std::to_string(i) + " has no entries");
+    }
+    const int64_t nnz = row_ptr[m];
+    TSNE_REQUIRE(nnz == 0 || (col && P), "NULL buffer");
+    for (int64_t e = 0; e < nnz; ++e)
+        if (col[e] < 0 || col[e] >= n) fail(TSNE_ERR_ARG, "column index out of range");
+}
+
+int tsne_knn_cross(tsne_ctx *ctx, const double *X, int64_t n, const double *Xq, int64_t m, int32_t d,
+                   int32_t metric, int32_t k, int32_t *idx_out, double *dist_out) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        TSNE_REQUIRE(n >= 1 && m >= 0 && d >= 1 && k >= 1, "bad sizes");
+        if (m == 0) return;
+        TSNE_REQUIRE(X && Xq && idx_out && dist_out, "NULL buffer");
+        const int64_t kk = std::min<int64_t>(k, n);
+        double *dX = upload(ctx, "h.X", X, (size_t)(n * d));
+        double *dQ = upload(ctx, "h.Xq", Xq, (size_t)(m * d));
+        int32_t *di = ctx->ws.get<int32_t>("h.knn_idx", (size_t)(m * kk));
+        double *dd = ctx->ws.get<double>("h.knn_dist", (size_t)(m * kk));
+        knn_cross_device(ctx, dX, n, dQ, m, d, metric, k, di, dd);
+        download(ctx, idx_out, di, (size_t)(m * kk));
+        download(ctx, dist_out, dd, (size_t)(m * kk));
+        sync(ctx);
+    });
+}
+
+int tsne_dev_knn_cross(tsne_ctx *ctx, const double *dX, int64_t n, const double *dXq, int64_t m, int32_t d,
+                       int32_t metric, int32_t k, int32_t *d_idx, double *d_dist) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        knn_cross_device(ctx, dX, n, dXq, m, d, metric, k, d_idx, d_dist);
+    });
+}
+
+int tsne_repulsion_queries(tsne_ctx *ctx, const double *Y, int64_t n, double theta, const double *Q, int64_t m,
+                           double *F_out, double *z_out) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        TSNE_REQUIRE(Y && n >= 1 && m >= 0, "bad arguments");
+        if (m == 0) return;
+        TSNE_REQUIRE(Q && F_out && z_out, "NULL buffer");
+        double *dY = upload(ctx, "h.Y", Y, (size_t)n * 2);
+        double *dQ = upload(ctx, "h.Q", Q, (size_t)m * 2);
+        double *dF = ctx->ws.get<double>("h.qF", (size_t)m * 2);
+        double *dz = ctx->ws.get<double>("h.qz", (size_t)m);
+        repulsion_queries_device(ctx, dY, n, theta, dQ, m, dF, dz);
+        download(ctx, F_out, dF, (size_t)m * 2);
+        download(ctx, z_out, dz, (size_t)m);
+        walk_flag_check(ctx, "bhx1.");
+    });
+}
+
+int tsne_dev_repulsion_queries(tsne_ctx *ctx, const double *dY, int64_t n, double theta, const double *dQ,
+                               int64_t m, double *d_F, double *d_z) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        TSNE_REQUIRE(m == 0 || (dY && dQ && d_F && d_z), "NULL buffer");
+        repulsion_queries_device(ctx, dY, n, theta, dQ, m, d_F, d_z);
+    });
+}
+
+int tsne_transform_init(tsne_ctx *ctx, const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m,
+                        const double *Yref, int64_t n, double *Y_out) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        TSNE_REQUIRE(m >= 0 && n >= 1, "bad sizes");
+        if (m == 0) return;
+        TSNE_REQUIRE(Yref && Y_out, "NULL buffer");
+        check_cross_csr(row_ptr, col, P, m, n, true);
+        const int64_t nnz = row_ptr[m];
+        int64_t *drp = upload(ctx, "h.xrp", row_ptr, (size_t)m + 1);
+        int32_t *dc = upload(ctx, "h.xcol", col, (size_t)nnz);
+        double *dp = upload(ctx, "h.xp", P, (size_t)nnz);
+        double *dYr = upload(ctx, "h.xYref", Yref, (size_t)n * 2);
+        double *dY = ctx->ws.get<double>("h.xY", (size_t)m * 2);
+        transform_init_device(ctx, drp, dc, dp, m, dYr, n, dY);
+        download(ctx, Y_out, dY, (size_t)m * 2);
+        sync(ctx);
+    });
+}
+
+int tsne_transform(tsne_ctx *ctx, const tsne_params *params, const double *Yref, int64_t n,
+                   const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m, double *Y, double *upd,
+                   double *gains, int32_t *loss_keys, double *loss_vals, int32_t loss_cap, int32_t *n_loss) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        TSNE_REQUIRE(params != nullptr, "params is NULL");
+        if (params->n_components != 2) fail(TSNE_ERR_UNSUPPORTED, "the transform is 2-D only (n_components must be 2)");
+        TSNE_REQUIRE(m >= 0 && n >= 1, "bad sizes");
+        if (n_loss) *n_loss = 0;
+        if (m == 0) return;
+        TSNE_REQUIRE(Yref && Y && upd && gains, "NULL buffer");
+        check_cross_csr(row_ptr, col, P, m, n, false);
+        const int64_t nnz = row_ptr[m];
+        int64_t *drp = upload(ctx, "h.xrp", row_ptr, (size_t)m + 1);
+        int32_t *dc = upload(ctx, "h.xcol", col, (size_t)nnz);
+        double *dp = upload(ctx, "h.xp", P, (size_t)nnz);
+        double *dYr = upload(ctx, "h.xYref", Yref, (size_t)n * 2);
+        double *dY = upload(ctx, "h.xY", Y, (size_t)m * 2);
+        double *du = upload(ctx, "h.xupd", upd, (size_t)m * 2);
+        double *dn = upload(ctx, "h.xgains", gains, (size_t)m * 2);
+        transform_setup(ctx, params, dYr, n, drp, dc, dp, m, dY, du, dn);
+        for (int32_t t = 1; t <= params->iterations; ++t) transform_step(ctx, t);
+        transform_sync(ctx);
+        download(ctx, Y, dY, (size_t)m * 2);
+        download(ctx, upd, du, (size_t)m * 2);
+        download(ctx, gains, dn, (size_t)m * 2);
+        sync(ctx);
+        const int32_t k = transform_losses(ctx, loss_keys, loss_vals, loss_cap);
+        if (n_loss) *n_loss = k;
+    });
+}
+
+int tsne_dev_transform_setup(tsne_ctx *ctx, const tsne_params *params, const double *d_Yref, int64_t n,
+                             const int64_t *d_row_ptr, const int32_t *d_col, const double *d_P, int64_t m,
+                             double *d_Y, double *d_upd, double *d_gains) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        transform_setup(ctx, params, d_Yref, n, d_row_ptr, d_col, d_P, m, d_Y, d_upd, d_gains);
+    });
+}
+
+int tsne_dev_transform_step(tsne_ctx *ctx, int32_t t) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        transform_step(ctx, t);
+    });
+}
+
+int tsne_dev_transform_sync(tsne_ctx *ctx) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        transform_sync(ctx);
+    });
+}
+
+int tsne_dev_transform_losses(tsne_ctx *ctx, int32_t *loss_keys, double *loss_vals, int32_t cap, int32_t *n_loss) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        const int32_t k = transform_losses(ctx, loss_keys, loss_vals, cap);
+        if (n_loss) *n_loss = k;
     });
 }
 

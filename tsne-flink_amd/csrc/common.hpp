@@ -158,6 +158,7 @@ struct StageTimers {
 struct Comm;      // collective backend: RCCL or in-process loopback (comm.cpp)
 struct OptState;  // device-resident optimizer state (optimize.hip)
 struct BHTree;    // Barnes-Hut tree (bhtree.hpp)
+struct TransformState;  // embedding new points into a fitted map (transform.hpp)
 
 // Per-context tunables (tsne_ctx_set_option): the library's defaults, set per
 // handle by the caller -- nothing here is process-static.  DESIGN.md 3a gives
@@ -225,6 +226,10 @@ struct Options {
                                  // through this build's Morton order (made during the build, second stream)
     int trav_prio = 0;           // 1-3: the 64-query BH traversal's waves at that issue priority (s_setprio)
     int tile_stream_gate = 1;    // 1: the consumers wait (on the device) until every traversal block has started
+    int transform_resort = 10;   // transform steps between Morton sorts of the new points (0: only at setup; no
+                                 // result depends on it, transform.hip "Canonical order")
+    int transform_split = 0;     // 1: a transform step as two launches (walk, then attraction + update; the same
+                                 // bits) instead of the fused one (A/B)
 };
 
 }  // namespace tsne
@@ -244,6 +249,8 @@ struct tsne_ctx {
     tsne::OptState *opt = nullptr;
     tsne::Options opts;
     tsne::BHTree *single_tree = nullptr;   // bh_single_tree (owned; freed by tsne_ctx_destroy)
+    tsne::BHTree *query_tree = nullptr;    // tsne_repulsion_queries' tree ("bhx1."; owned, freed by tsne_ctx_destroy)
+    tsne::TransformState *xform = nullptr; // tsne_dev_transform_* state with its own tree ("bhx."; transform_destroy)
     std::string loop_profile_pending;      // tsne_ctx_loop_profile: a summary read for its length, not yet copied out
     tsne::StageTimers timers;
     int32_t *pinned = nullptr;   // small pinned host scratch (per-iteration read-backs)
@@ -275,6 +282,9 @@ inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 // ---- stage entry points (device pointers, enqueue on ctx->stream) ----
 void knn_device(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t metric,
                 int32_t k, int64_t q0, int64_t q1, int32_t *d_idx, double *d_dist);
+// the m rows of dXq against the n rows of dX (no candidate excluded): m x min(k, n)
+void knn_cross_device(tsne_ctx *ctx, const double *dX, int64_t n, const double *dXq, int64_t m, int32_t d,
+                      int32_t metric, int32_t k, int32_t *d_idx, double *d_dist);
 void project_knn_device(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t metric, int32_t k,
                         int32_t iterations, const double *d_shifts, int32_t *d_idx, double *d_dist);
 void affinities_device(tsne_ctx *ctx, const int64_t *d_row_ptr, const double *d_dist,

@@ -22,6 +22,8 @@
 //   5. fallback: a query whose buffer overflows (only pathological crowds of
 //              near-equal distances, e.g. many duplicate points) is redone by
 //              an exact fp64 scan + stable radix sort.
+#include <algorithm>
+
 #include <hipcub/hipcub.hpp>
 
 #include "common.hpp"
@@ -685,9 +687,15 @@ __global__ void fill_f32(float *p, int64_t n, float v) {
     if (i < n) p[i] = v;
 }
 
+// Rows [0, n) of dX are prepared (centred about their common mean, split);
+// the candidates are the rows [0, nc), the queries the rows [q0, q1).
+// tsne_knn: nc = n (a query's own row is excluded by the filters' c != q);
+// the cross form stacks the query rows behind the nc reference rows, so no
+// candidate is a query.  scan_only: every query takes the exact fp64 scan
+// (kk beyond the candidate buffers' capacity).
 template <int CAP>
-void knn_run(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t metric, int32_t kk,
-             int64_t q0, int64_t q1, int32_t *d_idx, double *d_dist) {
+void knn_run(tsne_ctx *ctx, const double *dX, int64_t n, int64_t nc, int32_t d, int32_t metric, int32_t kk,
+             int64_t q0, int64_t q1, int32_t *d_idx, double *d_dist, bool scan_only = false) {
     hipStream_t st = ctx->stream;
     Workspace &ws = ctx->ws;
     const int64_t nq = q1 - q0;
@@ -742,11 +750,14 @@ void knn_run(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t metr
     float *cand_d = ws.get<float>("knn.cand_d", (size_t)nq * CAP);
     int32_t *cand_j = ws.get<int32_t>("knn.cand_j", (size_t)nq * CAP);
     TSNE_HIP(hipMemsetAsync(flags, 0, nq * sizeof(int32_t), st));
-
+    std::vector<int32_t> hflags(nq);
+    if (scan_only) {
+        std::fill(hflags.begin(), hflags.end(), 1);
+    } else {
     const int64_t qtiles = ceil_div(nq, TQ);
     // dense first range
     int64_t s0 = round_up(std::max<int64_t>(kk + 1, 256), TC);
-    s0 = std::min<int64_t>(std::min<int64_t>(s0, CAP), n);
+    s0 = std::min<int64_t>(std::min<int64_t>(s0, CAP), nc);
     hipLaunchKernelGGL(fill_i32, dim3(ceil_div(nq, 256)), dim3(256), 0, st, cnt, nq, (int32_t)s0);
     // "knn.filter": the MFMA filter launches alone (their sum is the kNN's
     // dense-contraction time, tsne_ctx_stage_ms)
@@ -764,8 +775,8 @@ void knn_run(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t metr
     };
     compact();
     int64_t seen = s0;
-    while (seen < n) {
-        int64_t r = std::min<int64_t>(seen, n - seen);
+    while (seen < nc) {
+        int64_t r = std::min<int64_t>(seen, nc - seen);
         ctx->timers.begin("knn.filter", st);
         if (use_bf)
             hipLaunchKernelGGL(knn_filter_glds,
@@ -786,25 +797,25 @@ void knn_run(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t metr
     TSNE_LAUNCH_CHECK();
 
     // --- exact fallback for flagged queries
-    std::vector<int32_t> hflags(nq);
     TSNE_HIP(hipMemcpyAsync(hflags.data(), flags, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TSNE_HIP(hipStreamSynchronize(st));
+    }
     bool any = false;
     for (int64_t i = 0; i < nq && !any; ++i) any = hflags[i] != 0;
     if (!any) return;
-    uint64_t *keys = ws.get<uint64_t>("knn.fb_keys", n);
-    uint64_t *keys2 = ws.get<uint64_t>("knn.fb_keys2", n);
-    int32_t *vals = ws.get<int32_t>("knn.fb_vals", n);
-    int32_t *vals2 = ws.get<int32_t>("knn.fb_vals2", n);
-    double *dist = ws.get<double>("knn.fb_dist", n);
+    uint64_t *keys = ws.get<uint64_t>("knn.fb_keys", nc);
+    uint64_t *keys2 = ws.get<uint64_t>("knn.fb_keys2", nc);
+    int32_t *vals = ws.get<int32_t>("knn.fb_vals", nc);
+    int32_t *vals2 = ws.get<int32_t>("knn.fb_vals2", nc);
+    double *dist = ws.get<double>("knn.fb_dist", nc);
     size_t tmp_bytes = 0;
-    TSNE_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, vals, vals2, (int)n, 0, 64, st));
+    TSNE_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, vals, vals2, (int)nc, 0, 64, st));
     void *tmp = ws.get<uint8_t>("knn.fb_tmp", tmp_bytes);
     for (int64_t i = 0; i < nq; ++i) {
         if (!hflags[i]) continue;
-        hipLaunchKernelGGL(fallback_dist, dim3(ceil_div(n, 256)), dim3(256), 0, st, dX, n, d, metric,
+        hipLaunchKernelGGL(fallback_dist, dim3(ceil_div(nc, 256)), dim3(256), 0, st, dX, nc, d, metric,
                            norm64, q0 + i, keys, vals, dist);
-        TSNE_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys2, vals, vals2, (int)n, 0, 64, st));
+        TSNE_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys2, vals, vals2, (int)nc, 0, 64, st));
         hipLaunchKernelGGL(fallback_emit, dim3(ceil_div(kk, 256)), dim3(256), 0, st, keys2, vals2, dist,
                            kk, d_idx + i * kk, d_dist + i * kk);
         TSNE_LAUNCH_CHECK();
@@ -824,11 +835,43 @@ void knn_device(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t m
     const int32_t kk = (int32_t)std::min<int64_t>(k, n - 1);
     if (q1 == q0) return;
     if (4 * kk + 256 <= 1024)
-        knn_run<1024>(ctx, dX, n, d, metric, kk, q0, q1, d_idx, d_dist);
+        knn_run<1024>(ctx, dX, n, n, d, metric, kk, q0, q1, d_idx, d_dist);
     else if (4 * kk + 512 <= 4096)
-        knn_run<4096>(ctx, dX, n, d, metric, kk, q0, q1, d_idx, d_dist);
+        knn_run<4096>(ctx, dX, n, n, d, metric, kk, q0, q1, d_idx, d_dist);
     else
         fail(TSNE_ERR_UNSUPPORTED, "k too large (max 896)");
+}
+
+// Cross kNN: for each of the m rows of dXq the min(k, n) nearest rows of dX,
+// ascending by (exact fp64 metric, j), no candidate excluded.  The rows are
+// stacked ([X; Xq], one workspace copy) and ranked by knn_run with the
+// candidates [0, n) and the queries [n, n + m), in slices of XQ_SLICE queries
+// (the candidate buffers are per query).  k beyond the filters' capacity
+// takes the exact scan for every query.
+void knn_cross_device(tsne_ctx *ctx, const double *dX, int64_t n, const double *dXq, int64_t m, int32_t d,
+                      int32_t metric, int32_t k, int32_t *d_idx, double *d_dist) {
+    TSNE_REQUIRE(n >= 1 && m >= 0, "cross kNN needs at least one reference row");
+    TSNE_REQUIRE(d >= 1, "dimension must be positive");
+    TSNE_REQUIRE(k >= 1, "k must be positive");
+    TSNE_REQUIRE(metric >= 0 && metric <= 2, "unknown metric");
+    TSNE_REQUIRE(n + m < (int64_t)INT32_MAX, "n + m must fit int32 point ids");
+    if (m == 0) return;
+    const int32_t kk = (int32_t)std::min<int64_t>(k, n);
+    double *S = ctx->ws.get<double>("knn.xstack", (size_t)(n + m) * d);
+    TSNE_HIP(hipMemcpyAsync(S, dX, sizeof(double) * (size_t)n * d, hipMemcpyDeviceToDevice, ctx->stream));
+    TSNE_HIP(hipMemcpyAsync(S + n * d, dXq, sizeof(double) * (size_t)m * d, hipMemcpyDeviceToDevice, ctx->stream));
+    constexpr int64_t XQ_SLICE = 1 << 17;
+    for (int64_t a = 0; a < m; a += XQ_SLICE) {
+        const int64_t b = std::min(m, a + XQ_SLICE);
+        int32_t *oi = d_idx + a * kk;
+        double *od = d_dist + a * kk;
+        if (4 * kk + 256 <= 1024)
+            knn_run<1024>(ctx, S, n + m, n, d, metric, kk, n + a, n + b, oi, od);
+        else if (4 * kk + 512 <= 4096)
+            knn_run<4096>(ctx, S, n + m, n, d, metric, kk, n + a, n + b, oi, od);
+        else
+            knn_run<1024>(ctx, S, n + m, n, d, metric, kk, n + a, n + b, oi, od, true);
+    }
 }
 
 }  // namespace tsne

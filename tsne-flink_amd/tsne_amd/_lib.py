@@ -86,6 +86,16 @@ SIGNATURES = {
     "tsne_ctx_counter": (C.c_int, [P, C.c_char_p, PI64]),
     "tsne_debug_wave_log": (C.c_int, [P, P, I64, PI64]),
     "tsne_ctx_loop_profile": (C.c_int, [P, C.c_char_p, I64, PI64]),
+    "tsne_knn_cross": (C.c_int, [P, P, I64, P, I64, I32, I32, I32, P, P]),
+    "tsne_dev_knn_cross": (C.c_int, [P, P, I64, P, I64, I32, I32, I32, P, P]),
+    "tsne_repulsion_queries": (C.c_int, [P, P, I64, D, P, I64, P, P]),
+    "tsne_dev_repulsion_queries": (C.c_int, [P, P, I64, D, P, I64, P, P]),
+    "tsne_transform_init": (C.c_int, [P, P, P, P, I64, P, I64, P]),
+    "tsne_transform": (C.c_int, [P, C.POINTER(Params), P, I64, P, P, P, I64, P, P, P, P, P, I32, PI32]),
+    "tsne_dev_transform_setup": (C.c_int, [P, C.POINTER(Params), P, I64, P, P, P, I64, P, P, P]),
+    "tsne_dev_transform_step": (C.c_int, [P, I32]),
+    "tsne_dev_transform_sync": (C.c_int, [P]),
+    "tsne_dev_transform_losses": (C.c_int, [P, P, P, I32, PI32]),
 }
 
 _lib = None

@@ -315,7 +315,93 @@ class Context:
                                   _ptr(upd), _ptr(gains), _ptr(keys), _ptr(vals), cap, C.byref(nl)))
         return dict(zip(keys[:nl.value].tolist(), vals[:nl.value].tolist()))
 
+    # ---- embedding new points into a fitted map (host buffers)
+    def kNearestNeighborsCross(self, X, Xq, k, metric="sqeuclidean"):
+        """tsne_knn_cross: the min(k, n) nearest rows of X for every row of Xq, no
+        candidate excluded -> (idx[m, kk] int32, dist[m, kk] f64)."""
+        X, Xq = _f64(X), _f64(Xq)
+        (n, d), m = X.shape, Xq.shape[0]
+        if Xq.ndim != 2 or Xq.shape[1] != d:
+            raise ValueError("Xq has shape %s, expected (m, %d)" % (Xq.shape, d))
+        kk = min(k, n)
+        idx = np.zeros((m, kk), dtype=np.int32)
+        dist = np.zeros((m, kk), dtype=np.float64)
+        check(lib().tsne_knn_cross(self._h, _ptr(X), n, _ptr(Xq), m, d, METRICS[metric], k, _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def repulsionQueries(self, Y, theta, Q):
+        """tsne_repulsion_queries: computeRepulsiveForce of the tree of Y for the
+        points Q, which are not in it -> (F[m, 2], z[m]) in the order of Q."""
+        Y, Q = _f64(Y), _f64(Q)
+        if Y.ndim != 2 or Y.shape[1] != 2 or Q.ndim != 2 or Q.shape[1] != 2:
+            raise ValueError("Y and Q must be n x 2 and m x 2")
+        m = Q.shape[0]
+        F = np.zeros((m, 2))
+        z = np.zeros(m)
+        check(lib().tsne_repulsion_queries(self._h, _ptr(Y), Y.shape[0], theta, _ptr(Q), m, _ptr(F), _ptr(z)))
+        return F, z
+
+    def transformInit(self, row_ptr, col, P, Y_ref):
+        """tsne_transform_init: the P-weighted mean of each new point's neighbours
+        on the map -> Y[m, 2]."""
+        Y_ref = _f64(Y_ref)
+        m = len(row_ptr) - 1
+        rp, cl, pv = _csr(row_ptr, col, P, m)   # converted copies stay referenced across the call
+        Y = np.zeros((m, 2))
+        check(lib().tsne_transform_init(self._h, _ptr(rp), _ptr(cl), _ptr(pv), m, _ptr(Y_ref), Y_ref.shape[0],
+                                        _ptr(Y)))
+        return Y
+
+    def transform(self, Y_ref, row_ptr, col, P, Y, upd, gains, params):
+        """tsne_transform: params.iterations iterations that move only the new
+        points, in place on Y / upd / gains (m x 2); returns {iteration: loss}."""
+        Y_ref = _f64(Y_ref)
+        m = Y.shape[0]
+        _inout(m, 2, Y=Y, upd=upd, gains=gains)   # written in place by the library
+        rp, cl, pv = _csr(row_ptr, col, P, m)
+        cap = params.iterations // 10 + 1
+        keys = np.zeros(cap, dtype=np.int32)
+        vals = np.zeros(cap)
+        nl = C.c_int32()
+        check(lib().tsne_transform(self._h, C.byref(params), _ptr(Y_ref), Y_ref.shape[0], _ptr(rp), _ptr(cl),
+                                   _ptr(pv), m, _ptr(Y), _ptr(upd), _ptr(gains), _ptr(keys), _ptr(vals), cap,
+                                   C.byref(nl)))
+        k = min(nl.value, cap)
+        return dict(zip(keys[:k].tolist(), vals[:k].tolist()))
+
     # ---- device operators (torch CUDA tensors)
+    def dev_knn_cross(self, dX, dXq, k, metric, d_idx, d_dist):
+        self._fence(dX)
+        (n, d), m = dX.shape, dXq.shape[0]
+        check(lib().tsne_dev_knn_cross(self._h, _ptr(dX), n, _ptr(dXq), m, d, METRICS[metric], k, _ptr(d_idx),
+                                       _ptr(d_dist)))
+
+    def dev_repulsion_queries(self, dY, theta, dQ, dF, dz):
+        self._fence(dY)
+        check(lib().tsne_dev_repulsion_queries(self._h, _ptr(dY), dY.shape[0], theta, _ptr(dQ), dQ.shape[0],
+                                               _ptr(dF), _ptr(dz)))
+
+    def dev_transform_setup(self, params, dY_ref, d_row_ptr, d_col, d_P, dY, dupd, dgains):
+        """The tensors are used in place until the last step: keep them alive."""
+        self._fence(dY)
+        check(lib().tsne_dev_transform_setup(self._h, C.byref(params), _ptr(dY_ref), dY_ref.shape[0],
+                                             _ptr(d_row_ptr), _ptr(d_col), _ptr(d_P), dY.shape[0], _ptr(dY),
+                                             _ptr(dupd), _ptr(dgains)))
+
+    def dev_transform_step(self, t):
+        check(lib().tsne_dev_transform_step(self._h, t))
+
+    def dev_transform_sync(self):
+        check(lib().tsne_dev_transform_sync(self._h))
+
+    def dev_transform_losses(self, cap=1024):
+        keys = np.zeros(cap, dtype=np.int32)
+        vals = np.zeros(cap)
+        nl = C.c_int32()
+        check(lib().tsne_dev_transform_losses(self._h, _ptr(keys), _ptr(vals), cap, C.byref(nl)))
+        k = min(nl.value, cap)
+        return dict(zip(keys[:k].tolist(), vals[:k].tolist()))
+
     def dev_knn(self, dX, k, metric, q0, q1, d_idx, d_dist):
         self._fence(dX)
         n, d = dX.shape
@@ -389,6 +475,32 @@ class Context:
         cnt = np.zeros(10, dtype=np.int64)
         check(lib().tsne_dev_opt_profile(self._h, enable, _ptr(ms), _ptr(cnt)))
         return ms, cnt.tolist()
+
+
+def transform(ctx, X_ref, Y_ref, X_new, k, perplexity, metric="sqeuclidean", params=None):
+    """Embed the rows of X_new into the fitted map Y_ref of X_ref, which stays
+    fixed: cross kNN -> pairwiseAffinities on the cross distances (conditional
+    p_{j|i}, not symmetrised) -> transformInit -> Context.transform.
+    Returns (Y_new[m, 2], {iteration: loss}).
+
+    params: default_params() with learning_rate = 1.0, NOT the fit's 1000 -- every
+    new point is normalised by its own z_i, so its gradient is of order 1.  On
+    the 2000-point test map (tests/test_gpu_transform.py) 1.0 was stable and 10
+    diverged (max |Y| 46 -> 637); nothing else has been tuned."""
+    X_ref, Y_ref, X_new = _f64(X_ref), _f64(Y_ref), _f64(X_new)
+    if params is None:
+        params = default_params(learning_rate=1.0, metric=metric)
+    m = X_new.shape[0]
+    if m == 0:
+        return np.zeros((0, 2)), {}
+    idx, dist = ctx.kNearestNeighborsCross(X_ref, X_new, k, metric)
+    kk = idx.shape[1]
+    rp = np.arange(0, m * kk + 1, kk, dtype=np.int64)
+    P = ctx.pairwiseAffinities(rp, dist.ravel(), perplexity)
+    Y = ctx.transformInit(rp, idx.ravel(), P, Y_ref)
+    upd, gains = np.zeros_like(Y), np.ones_like(Y)
+    losses = ctx.transform(Y_ref, rp, idx.ravel(), P, Y, upd, gains, params)
+    return Y, losses
 
 
 def project_shifts(iterations, d, seed=0):
