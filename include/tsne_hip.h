@@ -223,7 +223,11 @@ int tsne_ctx_synchronize(tsne_ctx *ctx);
  *   "transform_split" 0       1: a transform step as two launches (the walk,
  *                             then attraction + update) instead of the fused
  *                             one; the same bits (an A/B);
- *   "loop_serial" 0          1 (a loopback tsne_ctx_create_multi group, set
+ *   "transform_stats" 0       1: tsne_[dev_]repulsion_queries_c on a 3-D map
+ *                             counts its walk's stack pops, read with the
+ *                             "xform3.pops" counter below (a measurement aid;
+ *                             the same sums);
+ *   "loop_serial" 0         1 (a loopback tsne_ctx_create_multi group, set
  *                             before tsne_optimize): the ranks take turns on the
  *                             device and log their work between collectives --
  *                             a one-GPU projection of N GPUs, read with
@@ -287,7 +291,10 @@ int tsne_ctx_loop_profile(tsne_ctx *ctx, char *buf, int64_t cap, int64_t *len_ou
  *                        exhausted (those walks went on unsplit / untiled: the
  *                        same sums, but their split points then depend on timing);
  *   "bh.stream_lists", "opt.stream_lists"  tile lists the streaming consumers
- *                        summed (option "tile_stream"), over every traversal. */
+ *                        summed (option "tile_stream"), over every traversal;
+ *   "xform3.pops"        with option "transform_stats": stack pops (wave level,
+ *                        64 queries per wave) of the last 3-D
+ *                        tsne_[dev_]repulsion_queries_c walk. */
 int tsne_ctx_counter(tsne_ctx *ctx, const char *name, int64_t *value_out);
 
 /* Diagnostics (option "wave_log" with "rep_stats"): the last counting
@@ -480,8 +487,10 @@ int tsne_ctx_stage_ms(tsne_ctx *ctx, const char *stage, double *ms_out, int32_t 
 /* ------------------------------------- embedding new points into a fitted map */
 /* The reference embedding Yref (n x 2) stays fixed; m new points are placed
  * into it.  Not in the reference job (which only fits): the pieces are the
- * reference's own operators applied across two point sets.  2-D only.  On a
- * tsne_ctx_create_multi handle these run on the first device. */
+ * reference's own operators applied across two point sets.  The entry points
+ * without a suffix are 2-D; the _c forms further down take the map's dimension
+ * c = 2 or 3.  On a tsne_ctx_create_multi handle these run on the first
+ * device. */
 
 /* Cross kNN: for each of the m rows of Xq (m x d) the min(k, n) nearest rows
  * of X (n x d), ascending by (exact fp64 breeze metric, j).  No candidate is
@@ -542,6 +551,37 @@ int tsne_dev_transform_step(tsne_ctx *ctx, int32_t t);
 int tsne_dev_transform_sync(tsne_ctx *ctx);
 int tsne_dev_transform_losses(tsne_ctx *ctx, int32_t *loss_keys, double *loss_vals, int32_t cap,
                               int32_t *n_loss);
+
+/* The same operators with an explicit map dimension c (the tsne_gradient_c
+ * precedent).  c == 2 runs the 2-D path above, bit for bit.  c == 3 runs over
+ * the octree of the map (the 3-D extension of the reference tree: root
+ * Cell(0, 0, 0, W), W the largest of the three extents, criterion h / D <
+ * theta with D the squared 3-D distance; 21 levels per axis -- distinct map
+ * points that share a level-21 cell interact with a query directly; exact
+ * duplicates are counted as the reference's insert counts them: a splitting
+ * leaf re-inserts its point once).  Any other c is TSNE_ERR_UNSUPPORTED.  As in 2-D, no
+ * near-exact, tile or moment shortcut is used for foreign queries, and a
+ * query's result does not depend on the other queries of the call, bit for
+ * bit.
+ *   tsne_repulsion_queries_c: Y is n x c, Q m x c, F_out m x c, z_out m.
+ *   tsne_transform_init_c:    Yref n x c, Y_out m x c.
+ *   tsne_transform_c / tsne_dev_transform_setup_c: params->n_components (2 or
+ *     3) is the width of Yref, Y, upd and gains; otherwise the arguments and
+ *     results of tsne_transform / tsne_dev_transform_setup.
+ * tsne_dev_transform_step / _sync / _losses serve whichever state was set up
+ * last.  The host forms validate row_ptr and col as the 2-D ones do. */
+int tsne_repulsion_queries_c(tsne_ctx *ctx, const double *Y, int64_t n, int32_t c, double theta, const double *Q,
+                             int64_t m, double *F_out, double *z_out);
+int tsne_dev_repulsion_queries_c(tsne_ctx *ctx, const double *dY, int64_t n, int32_t c, double theta,
+                                 const double *dQ, int64_t m, double *d_F, double *d_z);
+int tsne_transform_init_c(tsne_ctx *ctx, const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m,
+                          const double *Yref, int64_t n, int32_t c, double *Y_out);
+int tsne_transform_c(tsne_ctx *ctx, const tsne_params *params, const double *Yref, int64_t n,
+                     const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m, double *Y, double *upd,
+                     double *gains, int32_t *loss_keys, double *loss_vals, int32_t loss_cap, int32_t *n_loss);
+int tsne_dev_transform_setup_c(tsne_ctx *ctx, const tsne_params *params, const double *d_Yref, int64_t n,
+                               const int64_t *d_row_ptr, const int32_t *d_col, const double *d_P, int64_t m,
+                               double *d_Y, double *d_upd, double *d_gains);
 
 #ifdef __cplusplus
 }

@@ -157,6 +157,7 @@ static const OptionField k_options[] = {
     {"build_fuse", nullptr, &Options::build_fuse, 0, 1},
     {"transform_resort", nullptr, &Options::transform_resort, 0, 1 << 30},
     {"transform_split", nullptr, &Options::transform_split, 0, 1},
+    {"transform_stats", nullptr, &Options::transform_stats, 0, 1},
 };
 static const OptionField &option_field(const char *key) {
     for (const OptionField &f : k_options)
@@ -448,6 +449,7 @@ int tsne_ctx_counter(tsne_ctx *ctx, const char *name, int64_t *value_out) {
         else if (k == "opt.stream_lists")
             *value_out = opt_tree(ctx) ? bh_stream_counter(ctx, *opt_tree(ctx)) : 0;
         else if (k.rfind("bh.", 0) == 0 && repulsion_stat(ctx, k, value_out)) {}
+        else if (k == "xform3.pops") *value_out = transform3_pops(ctx);
         else if (k == "comm.kind") *value_out = comm_counter(ctx, false);
         else if (k == "comm.calls") *value_out = comm_counter(ctx, true);
         else if (k == "opt.csort_oversized") *value_out = opt_tree(ctx) ? csort_oversized(ctx, opt_tree(ctx)->cs) : 0;
@@ -1001,43 +1003,75 @@ int tsne_dev_knn_cross(tsne_ctx *ctx, const double *dX, int64_t n, const double 
     });
 }
 
-int tsne_repulsion_queries(tsne_ctx *ctx, const double *Y, int64_t n, double theta, const double *Q, int64_t m,
-                           double *F_out, double *z_out) {
+// The operators below for a map of dimension c (2: the quadtree path of
+// transform.hip, 3: the octree path of transform3.hip); the entry points
+// without a suffix pass c = 2.
+static void check_map_dim(int32_t c) {
+    if (c != 2 && c != 3) fail(TSNE_ERR_UNSUPPORTED, "the map's dimension must be 2 or 3");
+}
+
+static int repulsion_queries_host(tsne_ctx *ctx, const double *Y, int64_t n, int32_t c, double theta, const double *Q,
+                                  int64_t m, double *F_out, double *z_out) {
     return guard([&] {
         check_ctx(ctx);
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
+        check_map_dim(c);
         TSNE_REQUIRE(Y && n >= 1 && m >= 0, "bad arguments");
         if (m == 0) return;
         TSNE_REQUIRE(Q && F_out && z_out, "NULL buffer");
-        double *dY = upload(ctx, "h.Y", Y, (size_t)n * 2);
-        double *dQ = upload(ctx, "h.Q", Q, (size_t)m * 2);
-        double *dF = ctx->ws.get<double>("h.qF", (size_t)m * 2);
+        double *dY = upload(ctx, "h.Y", Y, (size_t)n * c);
+        double *dQ = upload(ctx, "h.Q", Q, (size_t)m * c);
+        double *dF = ctx->ws.get<double>("h.qF", (size_t)m * c);
         double *dz = ctx->ws.get<double>("h.qz", (size_t)m);
-        repulsion_queries_device(ctx, dY, n, theta, dQ, m, dF, dz);
-        download(ctx, F_out, dF, (size_t)m * 2);
+        if (c == 3) repulsion_queries3_device(ctx, dY, n, theta, dQ, m, dF, dz);
+        else repulsion_queries_device(ctx, dY, n, theta, dQ, m, dF, dz);
+        download(ctx, F_out, dF, (size_t)m * c);
         download(ctx, z_out, dz, (size_t)m);
-        walk_flag_check(ctx, "bhx1.");
+        walk_flag_check(ctx, c == 3 ? "octx1." : "bhx1.");
     });
+}
+
+int tsne_repulsion_queries(tsne_ctx *ctx, const double *Y, int64_t n, double theta, const double *Q, int64_t m,
+                           double *F_out, double *z_out) {
+    return repulsion_queries_host(ctx, Y, n, 2, theta, Q, m, F_out, z_out);
+}
+
+int tsne_repulsion_queries_c(tsne_ctx *ctx, const double *Y, int64_t n, int32_t c, double theta, const double *Q,
+                             int64_t m, double *F_out, double *z_out) {
+    return repulsion_queries_host(ctx, Y, n, c, theta, Q, m, F_out, z_out);
 }
 
 int tsne_dev_repulsion_queries(tsne_ctx *ctx, const double *dY, int64_t n, double theta, const double *dQ,
                                int64_t m, double *d_F, double *d_z) {
+    return tsne_dev_repulsion_queries_c(ctx, dY, n, 2, theta, dQ, m, d_F, d_z);
+}
+
+int tsne_dev_repulsion_queries_c(tsne_ctx *ctx, const double *dY, int64_t n, int32_t c, double theta,
+                                 const double *dQ, int64_t m, double *d_F, double *d_z) {
     return guard([&] {
         check_ctx(ctx);
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
+        check_map_dim(c);
         TSNE_REQUIRE(m == 0 || (dY && dQ && d_F && d_z), "NULL buffer");
-        repulsion_queries_device(ctx, dY, n, theta, dQ, m, d_F, d_z);
+        if (c == 3) repulsion_queries3_device(ctx, dY, n, theta, dQ, m, d_F, d_z);
+        else repulsion_queries_device(ctx, dY, n, theta, dQ, m, d_F, d_z);
     });
 }
 
 int tsne_transform_init(tsne_ctx *ctx, const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m,
                         const double *Yref, int64_t n, double *Y_out) {
+    return tsne_transform_init_c(ctx, row_ptr, col, P, m, Yref, n, 2, Y_out);
+}
+
+int tsne_transform_init_c(tsne_ctx *ctx, const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m,
+                          const double *Yref, int64_t n, int32_t c, double *Y_out) {
     return guard([&] {
         check_ctx(ctx);
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
+        check_map_dim(c);
         TSNE_REQUIRE(m >= 0 && n >= 1, "bad sizes");
         if (m == 0) return;
         TSNE_REQUIRE(Yref && Y_out, "NULL buffer");
@@ -1046,23 +1080,29 @@ int tsne_transform_init(tsne_ctx *ctx, const int64_t *row_ptr, const int32_t *co
         int64_t *drp = upload(ctx, "h.xrp", row_ptr, (size_t)m + 1);
         int32_t *dc = upload(ctx, "h.xcol", col, (size_t)nnz);
         double *dp = upload(ctx, "h.xp", P, (size_t)nnz);
-        double *dYr = upload(ctx, "h.xYref", Yref, (size_t)n * 2);
-        double *dY = ctx->ws.get<double>("h.xY", (size_t)m * 2);
-        transform_init_device(ctx, drp, dc, dp, m, dYr, n, dY);
-        download(ctx, Y_out, dY, (size_t)m * 2);
+        double *dYr = upload(ctx, "h.xYref", Yref, (size_t)n * c);
+        double *dY = ctx->ws.get<double>("h.xY", (size_t)m * c);
+        if (c == 3) transform_init3_device(ctx, drp, dc, dp, m, dYr, n, dY);
+        else transform_init_device(ctx, drp, dc, dp, m, dYr, n, dY);
+        download(ctx, Y_out, dY, (size_t)m * c);
         sync(ctx);
     });
 }
 
-int tsne_transform(tsne_ctx *ctx, const tsne_params *params, const double *Yref, int64_t n,
-                   const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m, double *Y, double *upd,
-                   double *gains, int32_t *loss_keys, double *loss_vals, int32_t loss_cap, int32_t *n_loss) {
+// allow3: tsne_transform_c; tsne_transform keeps TSNE_ERR_UNSUPPORTED for n_components != 2
+static int transform_host(tsne_ctx *ctx, const tsne_params *params, const double *Yref, int64_t n,
+                          const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m, double *Y,
+                          double *upd, double *gains, int32_t *loss_keys, double *loss_vals, int32_t loss_cap,
+                          int32_t *n_loss, bool allow3) {
     return guard([&] {
         check_ctx(ctx);
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
         TSNE_REQUIRE(params != nullptr, "params is NULL");
-        if (params->n_components != 2) fail(TSNE_ERR_UNSUPPORTED, "the transform is 2-D only (n_components must be 2)");
+        if (!allow3 && params->n_components != 2)
+            fail(TSNE_ERR_UNSUPPORTED, "the transform is 2-D only (n_components must be 2)");
+        check_map_dim(params->n_components);
+        const size_t c = (size_t)params->n_components;
         TSNE_REQUIRE(m >= 0 && n >= 1, "bad sizes");
         if (n_loss) *n_loss = 0;
         if (m == 0) return;
@@ -1072,20 +1112,34 @@ int tsne_transform(tsne_ctx *ctx, const tsne_params *params, const double *Yref,
         int64_t *drp = upload(ctx, "h.xrp", row_ptr, (size_t)m + 1);
         int32_t *dc = upload(ctx, "h.xcol", col, (size_t)nnz);
         double *dp = upload(ctx, "h.xp", P, (size_t)nnz);
-        double *dYr = upload(ctx, "h.xYref", Yref, (size_t)n * 2);
-        double *dY = upload(ctx, "h.xY", Y, (size_t)m * 2);
-        double *du = upload(ctx, "h.xupd", upd, (size_t)m * 2);
-        double *dn = upload(ctx, "h.xgains", gains, (size_t)m * 2);
-        transform_setup(ctx, params, dYr, n, drp, dc, dp, m, dY, du, dn);
+        double *dYr = upload(ctx, "h.xYref", Yref, (size_t)n * c);
+        double *dY = upload(ctx, "h.xY", Y, (size_t)m * c);
+        double *du = upload(ctx, "h.xupd", upd, (size_t)m * c);
+        double *dn = upload(ctx, "h.xgains", gains, (size_t)m * c);
+        transform_setup(ctx, params, dYr, n, drp, dc, dp, m, dY, du, dn, allow3);
         for (int32_t t = 1; t <= params->iterations; ++t) transform_step(ctx, t);
         transform_sync(ctx);
-        download(ctx, Y, dY, (size_t)m * 2);
-        download(ctx, upd, du, (size_t)m * 2);
-        download(ctx, gains, dn, (size_t)m * 2);
+        download(ctx, Y, dY, (size_t)m * c);
+        download(ctx, upd, du, (size_t)m * c);
+        download(ctx, gains, dn, (size_t)m * c);
         sync(ctx);
         const int32_t k = transform_losses(ctx, loss_keys, loss_vals, loss_cap);
         if (n_loss) *n_loss = k;
     });
+}
+
+int tsne_transform(tsne_ctx *ctx, const tsne_params *params, const double *Yref, int64_t n,
+                   const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m, double *Y, double *upd,
+                   double *gains, int32_t *loss_keys, double *loss_vals, int32_t loss_cap, int32_t *n_loss) {
+    return transform_host(ctx, params, Yref, n, row_ptr, col, P, m, Y, upd, gains, loss_keys, loss_vals, loss_cap,
+                          n_loss, false);
+}
+
+int tsne_transform_c(tsne_ctx *ctx, const tsne_params *params, const double *Yref, int64_t n,
+                     const int64_t *row_ptr, const int32_t *col, const double *P, int64_t m, double *Y, double *upd,
+                     double *gains, int32_t *loss_keys, double *loss_vals, int32_t loss_cap, int32_t *n_loss) {
+    return transform_host(ctx, params, Yref, n, row_ptr, col, P, m, Y, upd, gains, loss_keys, loss_vals, loss_cap,
+                          n_loss, true);
 }
 
 int tsne_dev_transform_setup(tsne_ctx *ctx, const tsne_params *params, const double *d_Yref, int64_t n,
@@ -1096,6 +1150,17 @@ int tsne_dev_transform_setup(tsne_ctx *ctx, const tsne_params *params, const dou
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
         transform_setup(ctx, params, d_Yref, n, d_row_ptr, d_col, d_P, m, d_Y, d_upd, d_gains);
+    });
+}
+
+int tsne_dev_transform_setup_c(tsne_ctx *ctx, const tsne_params *params, const double *d_Yref, int64_t n,
+                               const int64_t *d_row_ptr, const int32_t *d_col, const double *d_P, int64_t m,
+                               double *d_Y, double *d_upd, double *d_gains) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        transform_setup(ctx, params, d_Yref, n, d_row_ptr, d_col, d_P, m, d_Y, d_upd, d_gains, true);
     });
 }
 

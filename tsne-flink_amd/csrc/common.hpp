@@ -158,6 +158,7 @@ struct StageTimers {
 struct Comm;      // collective backend: RCCL or in-process loopback (comm.cpp)
 struct OptState;  // device-resident optimizer state (optimize.hip)
 struct BHTree;    // Barnes-Hut tree (bhtree.hpp)
+struct OctTree;   // Barnes-Hut octree of a 3-D embedding (octree.hpp)
 struct TransformState;  // embedding new points into a fitted map (transform.hpp)
 
 // Per-context tunables (tsne_ctx_set_option): the library's defaults, set per
@@ -230,6 +231,8 @@ struct Options {
                                  // result depends on it, transform.hip "Canonical order")
     int transform_split = 0;     // 1: a transform step as two launches (walk, then attraction + update; the same
                                  // bits) instead of the fused one (A/B)
+    int transform_stats = 0;     // 1: tsne_[dev_]repulsion_queries_c on a 3-D map counts its walk's pops
+                                 // (tsne_ctx_counter "xform3.pops"; a measurement aid, no result depends on it)
 };
 
 }  // namespace tsne
@@ -250,7 +253,9 @@ struct tsne_ctx {
     tsne::Options opts;
     tsne::BHTree *single_tree = nullptr;   // bh_single_tree (owned; freed by tsne_ctx_destroy)
     tsne::BHTree *query_tree = nullptr;    // tsne_repulsion_queries' tree ("bhx1."; owned, freed by tsne_ctx_destroy)
-    tsne::TransformState *xform = nullptr; // tsne_dev_transform_* state with its own tree ("bhx."; transform_destroy)
+    tsne::OctTree *query_tree3 = nullptr;  // tsne_repulsion_queries_c's octree ("octx1."; freed by transform_destroy)
+    tsne::TransformState *xform = nullptr; // tsne_dev_transform_* state with its own tree ("bhx." / "octx.";
+                                           // transform_destroy)
     std::string loop_profile_pending;      // tsne_ctx_loop_profile: a summary read for its length, not yet copied out
     tsne::StageTimers timers;
     int32_t *pinned = nullptr;   // small pinned host scratch (per-iteration read-backs)

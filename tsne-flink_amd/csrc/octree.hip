@@ -28,8 +28,6 @@
 namespace tsne {
 namespace {
 
-constexpr int LEVELS3 = 21;                 // 63 key bits
-constexpr uint64_t OUT_KEY3 = 1ull << 63;   // outside the root cell: sorts last
 constexpr int STACK3 = 256;                 // single pops, <= 2 pushes each: depth-bounded
 constexpr int AGG3 = 12;                    // sx, sy, sz, x0, x1, y0, y1, z0, z1, hmin, cnt, rball
 
@@ -83,62 +81,13 @@ __global__ void bbox3_final(const double *__restrict__ part, int nb, double *__r
     }
 }
 
-// fixed-point digits away from cell boundaries (see bhtree.hip quant_digits):
-// 21 levels, band 1e-4 of a level-21 cell
-__device__ __forceinline__ bool quant21(double p, double W, uint32_t &q) {
-    const double t = (p + W) / (2.0 * W) * 2097152.0;   // 2^21
-    if (!(t >= 0.0 && t < 2097152.0)) return false;
-    const double f = floor(t);
-    const double fr = t - f;
-    if (fr < 1e-4 || fr > 1.0 - 1e-4) return false;
-    q = (uint32_t)f;
-    return true;
-}
-
-// digit c = 4 lower + 2 south + east, tried in ascending c (the child order)
+// (the Morton key itself: morton3_key, octree.hpp -- shared with the transform's query sort)
 __global__ void morton3_keys(const double *__restrict__ Y, int64_t n, const double *__restrict__ Wp,
                              uint64_t *__restrict__ keys, int32_t *__restrict__ idx, int32_t *__restrict__ meta) {
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i0 < n;
     const int64_t i = live ? i0 : n - 1;
-    const double W = *Wp;
-    const double px = Y[3 * i], py = Y[3 * i + 1], pz = Y[3 * i + 2];
-    double x = 0.0, y = 0.0, z = 0.0, h = W;
-    bool in = live && (__dsub_rn(x, h) <= px) && (__dadd_rn(x, h) >= px) && (__dsub_rn(y, h) <= py) &&
-              (__dadd_rn(y, h) >= py) && (__dsub_rn(z, h) <= pz) && (__dadd_rn(z, h) >= pz);
-    uint64_t key = 0;
-    uint32_t qx, qy, qz;
-    if (in && W > 0.0 && quant21(px, W, qx) && quant21(py, W, qy) && quant21(pz, W, qz)) {
-        for (int l = LEVELS3 - 1; l >= 0; --l) {
-            const uint32_t east = (qx >> l) & 1u, south = 1u - ((qy >> l) & 1u), lower = 1u - ((qz >> l) & 1u);
-            key = (key << 3) | (uint64_t)(4u * lower + 2u * south + east);
-        }
-    } else if (in) {
-        for (int l = 0; l < LEVELS3; ++l) {
-            const double nh = __dmul_rn(0.5, h);
-            const double xw = __dsub_rn(x, nh), xe = __dadd_rn(x, nh);
-            const double yn = __dadd_rn(y, nh), ys = __dsub_rn(y, nh);
-            const double zu = __dadd_rn(z, nh), zl = __dsub_rn(z, nh);
-            const bool inW = (__dsub_rn(xw, nh) <= px) && (__dadd_rn(xw, nh) >= px);
-            const bool inE = (__dsub_rn(xe, nh) <= px) && (__dadd_rn(xe, nh) >= px);
-            const bool inN = (__dsub_rn(yn, nh) <= py) && (__dadd_rn(yn, nh) >= py);
-            const bool inS = (__dsub_rn(ys, nh) <= py) && (__dadd_rn(ys, nh) >= py);
-            const bool inU = (__dsub_rn(zu, nh) <= pz) && (__dadd_rn(zu, nh) >= pz);
-            const bool inL = (__dsub_rn(zl, nh) <= pz) && (__dadd_rn(zl, nh) >= pz);
-            int c = 7;   // lower SE, or a rounding gap (see bhtree.hip)
-            for (int t = 0; t < 8; ++t) {
-                const bool ok = ((t & 1) ? inE : inW) && ((t & 2) ? inS : inN) && ((t & 4) ? inL : inU);
-                if (ok) { c = t; break; }
-            }
-            x = (c & 1) ? xe : xw;
-            y = (c & 2) ? ys : yn;
-            z = (c & 4) ? zl : zu;
-            h = nh;
-            key = (key << 3) | (uint64_t)c;
-        }
-    } else {
-        key = OUT_KEY3;
-    }
+    const uint64_t key = live ? morton3_key(Y[3 * i], Y[3 * i + 1], Y[3 * i + 2], *Wp) : OUT_KEY3;
     if (live) {
         keys[i] = key;
         idx[i] = (int32_t)i;
@@ -1394,7 +1343,7 @@ __global__ __launch_bounds__(256) void oct_traverse64(
 
 }  // namespace
 
-void oct_alloc(tsne_ctx *ctx, OctTree &t, int64_t n, const std::string &pre) {
+void oct_alloc(tsne_ctx *ctx, OctTree &t, int64_t n, const std::string &pre, bool records_only) {
     Workspace &ws = ctx->ws;
     t.n = n;
     t.keys = ws.get<uint64_t>(pre + "keys", n);
@@ -1421,6 +1370,7 @@ void oct_alloc(tsne_ctx *ctx, OctTree &t, int64_t n, const std::string &pre) {
     t.sort_tmp = ws.get<uint8_t>(pre + "sort_tmp", tb);
     csort_alloc(ctx, t.cs, n, pre);
     t.cs_primed = false;
+    if (records_only) return;   // no moments, no moment tasks
     t.mom = ws.get<double>(pre + "mom", (size_t)MOM3_K * n);
     t.mcnt = ws.get<int32_t>(pre + "mcnt", n);
     t.moff = ws.get<int32_t>(pre + "moff", n);
@@ -1446,7 +1396,7 @@ void oct_alloc(tsne_ctx *ctx, OctTree &t, int64_t n, const std::string &pre) {
 
 static double oct_near_dmax(const tsne_ctx *ctx, double theta, bool late);
 
-void oct_build(tsne_ctx *ctx, OctTree &t, const double *dY, double theta, bool late) {
+void oct_build(tsne_ctx *ctx, OctTree &t, const double *dY, double theta, bool late, bool records_only) {
     hipStream_t st = ctx->stream;
     const int64_t n = t.n;
     hipLaunchKernelGGL(bbox3_partial, dim3(t.bbox_blocks), dim3(256), 0, st, dY, n, t.bbox_part);
@@ -1471,9 +1421,13 @@ void oct_build(tsne_ctx *ctx, OctTree &t, const double *dY, double theta, bool l
                        t.agg, t.parent_leaf, t.parent_node, t.arrive);
     hipLaunchKernelGGL(set_root3, dim3(1), dim3(1), 0, st, t.meta);
     t.near_dmax = oct_near_dmax(ctx, theta, late);
-    if (ctx->opts.oct_records)
+    if (ctx->opts.oct_records || records_only)
         hipLaunchKernelGGL(build_orec, dim3(ceil_div(n, OREC_BLK)), dim3(OREC_BLK), 0, st, t.nodes, t.pos, t.meta,
                            inv_theta, t.near_dmax, t.orec);
+    if (records_only) {
+        TSNE_LAUNCH_CHECK();
+        return;
+    }
     // subtree moments (when the last traversal wanted them)
     hipLaunchKernelGGL(oct_mom_gate, dim3(1), dim3(1), 0, st, t.mom_flag);
     hipLaunchKernelGGL(oct_mom_count, dim3(ceil_div(n, 256)), dim3(256), 0, st, t.nodes, n, t.meta, t.mom_flag, t.mcnt);

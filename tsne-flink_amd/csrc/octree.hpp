@@ -49,6 +49,64 @@ struct __attribute__((aligned(16))) ORec {
 };
 static_assert(sizeof(ORec) % 16 == 0, "records are fetched in 16-byte pieces");
 
+constexpr int LEVELS3 = 21;                 // 63 key bits
+constexpr uint64_t OUT_KEY3 = 1ull << 63;   // outside the root cell: sorts last
+
+// fixed-point digits away from cell boundaries (see bhtree.hip quant_digits):
+// 21 levels, band 1e-4 of a level-21 cell
+__device__ __forceinline__ bool quant21(double p, double W, uint32_t &q) {
+    const double t = (p + W) / (2.0 * W) * 2097152.0;   // 2^21
+    if (!(t >= 0.0 && t < 2097152.0)) return false;
+    const double f = floor(t);
+    const double fr = t - f;
+    if (fr < 1e-4 || fr > 1.0 - 1e-4) return false;
+    q = (uint32_t)f;
+    return true;
+}
+
+// The octree's key of point (px, py, pz) in the root cell (0, 0, 0, W): one
+// device function for morton3_keys (octree.hip) and the transform's query sort
+// (transform3.hip).  Digit c = 4 lower + 2 south + east, tried in ascending c
+// (the child order).
+__device__ __forceinline__ uint64_t morton3_key(double px, double py, double pz, double W) {
+    double x = 0.0, y = 0.0, z = 0.0, h = W;
+    const bool in = (__dsub_rn(x, h) <= px) && (__dadd_rn(x, h) >= px) && (__dsub_rn(y, h) <= py) &&
+                    (__dadd_rn(y, h) >= py) && (__dsub_rn(z, h) <= pz) && (__dadd_rn(z, h) >= pz);
+    if (!in) return OUT_KEY3;
+    uint64_t key = 0;
+    uint32_t qx, qy, qz;
+    if (W > 0.0 && quant21(px, W, qx) && quant21(py, W, qy) && quant21(pz, W, qz)) {
+        for (int l = LEVELS3 - 1; l >= 0; --l) {
+            const uint32_t east = (qx >> l) & 1u, south = 1u - ((qy >> l) & 1u), lower = 1u - ((qz >> l) & 1u);
+            key = (key << 3) | (uint64_t)(4u * lower + 2u * south + east);
+        }
+        return key;
+    }
+    for (int l = 0; l < LEVELS3; ++l) {
+        const double nh = __dmul_rn(0.5, h);
+        const double xw = __dsub_rn(x, nh), xe = __dadd_rn(x, nh);
+        const double yn = __dadd_rn(y, nh), ys = __dsub_rn(y, nh);
+        const double zu = __dadd_rn(z, nh), zl = __dsub_rn(z, nh);
+        const bool inW = (__dsub_rn(xw, nh) <= px) && (__dadd_rn(xw, nh) >= px);
+        const bool inE = (__dsub_rn(xe, nh) <= px) && (__dadd_rn(xe, nh) >= px);
+        const bool inN = (__dsub_rn(yn, nh) <= py) && (__dadd_rn(yn, nh) >= py);
+        const bool inS = (__dsub_rn(ys, nh) <= py) && (__dadd_rn(ys, nh) >= py);
+        const bool inU = (__dsub_rn(zu, nh) <= pz) && (__dadd_rn(zu, nh) >= pz);
+        const bool inL = (__dsub_rn(zl, nh) <= pz) && (__dadd_rn(zl, nh) >= pz);
+        int c = 7;   // lower SE, or a rounding gap (see bhtree.hip)
+        for (int t = 0; t < 8; ++t) {
+            const bool ok = ((t & 1) ? inE : inW) && ((t & 2) ? inS : inN) && ((t & 4) ? inL : inU);
+            if (ok) { c = t; break; }
+        }
+        x = (c & 1) ? xe : xw;
+        y = (c & 2) ? ys : yn;
+        z = (c & 4) ? zl : zu;
+        h = nh;
+        key = (key << 3) | (uint64_t)c;
+    }
+    return key;
+}
+
 struct OctTree {
     int64_t n = 0;
     uint64_t *keys = nullptr, *keys_sorted = nullptr;
@@ -58,6 +116,8 @@ struct OctTree {
     double4 *pos = nullptr;                          // sorted positions (x, y, z, 0)
     OctNode *nodes = nullptr;
     ORec *orec = nullptr;                            // per binary node id, valid for real cells
+    ORec *vrec = nullptr;                            // transform3.hip's duplicate fix-up: virtual chain-top records
+                                                     // (ref n + node id); null without exact duplicates
     double near_dmax = 0.0;                          // the records' near-exact radius (this build)
     double *agg = nullptr;
     int32_t *parent_leaf = nullptr, *parent_node = nullptr, *arrive = nullptr;
@@ -82,10 +142,16 @@ struct OctTree {
 // Allocate (from ctx->ws, buffers named pre + field) for n points: the
 // optimizer's tree "oct.", the single-call operators' "oct1." (the coherent
 // sort reads the previous build's order, so two trees never share buffers).
-void oct_alloc(tsne_ctx *ctx, OctTree &t, int64_t n, const std::string &pre = "oct.");
+// records_only: a tree for the transform's foreign walk (transform3.hip),
+// which reads the octal records and no subtree moments -- the moment and
+// moment-task buffers are not allocated, and such a tree serves oct_build
+// (records_only) alone, not oct_repulsion.
+void oct_alloc(tsne_ctx *ctx, OctTree &t, int64_t n, const std::string &pre = "oct.", bool records_only = false);
 // Octree of all n points of Y (n x 3, device); late: the optimizer after
 // early exaggeration (the near-exact tolerance the records are built for).
-void oct_build(tsne_ctx *ctx, OctTree &t, const double *dY, double theta, bool late = false);
+// records_only: the records whatever Options::oct_records says, no moments.
+void oct_build(tsne_ctx *ctx, OctTree &t, const double *dY, double theta, bool late = false,
+               bool records_only = false);
 // Repulsion for the query slots [s0, s1) (sorted positions, or qlist[slot]:
 // a rank's own queries, ascending): F (n x 3, sorted order) and z written
 // at the sorted position (the near-exact tolerance of the build).

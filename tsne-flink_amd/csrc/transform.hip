@@ -12,6 +12,8 @@
 //                   launch -- walk, attraction over the point's CSR row,
 //                   gradient with the point's own normaliser z_i, update;
 //   * the host side: the query sort, the tree kept in the context, the loss.
+// A 3-D map takes the same walk over the octree's records (transform3.hip);
+// the host side here dispatches on the state's dimension.
 //
 // Canonical order.  A wave's 64 queries share one LDS stack of (record, lane
 // mask) entries.  The stack is strictly LIFO, one record per pop, and an
@@ -376,13 +378,13 @@ int32_t *sort_queries(tsne_ctx *ctx, const BHTree &t, const double *dQ, int64_t 
     return perm;
 }
 
+}  // namespace
+
 int32_t *walk_flag(tsne_ctx *ctx, const std::string &pre) {
     int32_t *f = ctx->ws.get<int32_t>(pre + "qflag", 1);
     TSNE_HIP(hipMemsetAsync(f, 0, sizeof(int32_t), ctx->stream));
     return f;
 }
-
-}  // namespace
 
 void walk_flag_check(tsne_ctx *ctx, const char *pre) {
     const std::string name = std::string(pre) + "qflag";
@@ -420,15 +422,19 @@ void transform_init_device(tsne_ctx *ctx, const int64_t *d_row_ptr, const int32_
 
 void transform_setup(tsne_ctx *ctx, const tsne_params *p, const double *d_Yref, int64_t n,
                      const int64_t *d_row_ptr, const int32_t *d_col, const double *d_P, int64_t m, double *d_Y,
-                     double *d_upd, double *d_gains) {
+                     double *d_upd, double *d_gains, bool allow3) {
     TSNE_REQUIRE(p != nullptr, "params is NULL");
-    if (p->n_components != 2) fail(TSNE_ERR_UNSUPPORTED, "the transform is 2-D only (n_components must be 2)");
+    if (!allow3 && p->n_components != 2)
+        fail(TSNE_ERR_UNSUPPORTED, "the transform is 2-D only (n_components must be 2)");
+    if (p->n_components != 2 && p->n_components != 3)
+        fail(TSNE_ERR_UNSUPPORTED, "the transform is 2-D or 3-D (n_components must be 2 or 3)");
     TSNE_REQUIRE(m >= 0 && n >= 1, "bad sizes");
     TSNE_REQUIRE(n < (int64_t)INT32_MAX && m < (int64_t)INT32_MAX, "n and m must fit int32 ids");
     TSNE_REQUIRE(p->iterations >= 0, "negative iteration count");
     if (!ctx->xform) ctx->xform = new TransformState();
     TransformState *s = ctx->xform;
     s->prm = *p;
+    s->dim = p->n_components;
     s->n = n;
     s->m = m;
     s->loss_keys.clear();
@@ -436,13 +442,18 @@ void transform_setup(tsne_ctx *ctx, const tsne_params *p, const double *d_Yref, 
     TSNE_REQUIRE(d_Yref && d_row_ptr && d_col && d_P && d_Y && d_upd && d_gains, "NULL buffer");
     s->Yref = d_Yref; s->row_ptr = d_row_ptr; s->col = d_col; s->P = d_P;
     s->Y = d_Y; s->upd = d_upd; s->gains = d_gains;
-    build_tree(ctx, s->tree, d_Yref, n, p->theta, "bhx.");
-    s->flag = walk_flag(ctx, "bhx.");
-    s->perm = sort_queries(ctx, s->tree, d_Y, m, "bhx.");
+    if (s->dim == 3) {
+        transform3_build(ctx, s);
+    } else {
+        build_tree(ctx, s->tree, d_Yref, n, p->theta, "bhx.");
+        s->flag = walk_flag(ctx, "bhx.");
+        s->perm = sort_queries(ctx, s->tree, d_Y, m, "bhx.");
+    }
     s->since_sort = 0;
-    s->lossq = ctx->ws.get<double>("bhx.lossq", m);
+    const std::string pre = s->dim == 3 ? "octx." : "bhx.";
+    s->lossq = ctx->ws.get<double>(pre + "lossq", m);
     s->loss_cap = p->iterations / 10 + 1;
-    s->loss_d = ctx->ws.get<double>("bhx.loss", s->loss_cap);
+    s->loss_d = ctx->ws.get<double>(pre + "loss", s->loss_cap);
 }
 
 void transform_step(tsne_ctx *ctx, int32_t t) {
@@ -456,11 +467,22 @@ void transform_step(tsne_ctx *ctx, int32_t t) {
     const double mom = t <= n1 ? p.initial_momentum : p.final_momentum;
     const bool loss = t % 10 == 0 && (int32_t)s->loss_keys.size() < s->loss_cap;
     if (ctx->opts.transform_resort > 0 && s->since_sort >= ctx->opts.transform_resort) {
-        s->perm = sort_queries(ctx, s->tree, s->Y, s->m, "bhx.");
+        if (s->dim == 3) transform3_sort(ctx, s);
+        else s->perm = sort_queries(ctx, s->tree, s->Y, s->m, "bhx.");
         s->since_sort = 0;
     }
     ++s->since_sort;
     hipStream_t st = ctx->stream;
+    if (s->dim == 3) {   // the octree walk and the three-component update (transform3.hip)
+        transform3_launch(ctx, s, ex, mom, loss);
+        if (loss) {
+            hipLaunchKernelGGL(xform_loss_reduce, dim3(1), dim3(1024), 0, st, s->lossq, s->m,
+                               s->loss_d + s->loss_keys.size());
+            s->loss_keys.push_back(t);
+        }
+        TSNE_LAUNCH_CHECK();
+        return;
+    }
     const dim3 grid(ceil_div(s->m, 64 * XWPB)), block(64 * XWPB);
     const XTree T = tree_view(s->tree);
     const auto Yr = reinterpret_cast<const double2 *>(s->Yref);
@@ -496,7 +518,7 @@ void transform_sync(tsne_ctx *ctx) {
     TransformState *s = ctx->xform;
     TSNE_REQUIRE(s != nullptr, "tsne_dev_transform_setup was not called");
     TSNE_HIP(hipStreamSynchronize(ctx->stream));
-    if (s->m) walk_flag_check(ctx, "bhx.");
+    if (s->m) walk_flag_check(ctx, s->dim == 3 ? "octx." : "bhx.");
 }
 
 int32_t transform_losses(tsne_ctx *ctx, int32_t *keys, double *vals, int32_t cap) {
@@ -517,6 +539,8 @@ void transform_destroy(tsne_ctx *ctx) {
     ctx->xform = nullptr;
     delete ctx->query_tree;
     ctx->query_tree = nullptr;
+    delete ctx->query_tree3;
+    ctx->query_tree3 = nullptr;
 }
 
 }  // namespace tsne

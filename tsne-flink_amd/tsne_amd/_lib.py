@@ -93,6 +93,11 @@ SIGNATURES = {
     "tsne_transform_init": (C.c_int, [P, P, P, P, I64, P, I64, P]),
     "tsne_transform": (C.c_int, [P, C.POINTER(Params), P, I64, P, P, P, I64, P, P, P, P, P, I32, PI32]),
     "tsne_dev_transform_setup": (C.c_int, [P, C.POINTER(Params), P, I64, P, P, P, I64, P, P, P]),
+    "tsne_repulsion_queries_c": (C.c_int, [P, P, I64, I32, D, P, I64, P, P]),
+    "tsne_dev_repulsion_queries_c": (C.c_int, [P, P, I64, I32, D, P, I64, P, P]),
+    "tsne_transform_init_c": (C.c_int, [P, P, P, P, I64, P, I64, I32, P]),
+    "tsne_transform_c": (C.c_int, [P, C.POINTER(Params), P, I64, P, P, P, I64, P, P, P, P, P, I32, PI32]),
+    "tsne_dev_transform_setup_c": (C.c_int, [P, C.POINTER(Params), P, I64, P, P, P, I64, P, P, P]),
     "tsne_dev_transform_step": (C.c_int, [P, I32]),
     "tsne_dev_transform_sync": (C.c_int, [P]),
     "tsne_dev_transform_losses": (C.c_int, [P, P, P, I32, PI32]),

@@ -44,6 +44,13 @@ def _inout(n, c, **arrays):
             raise ValueError("%s must be a C-contiguous float64 array of shape (%d, %d)" % (name, n, c))
 
 
+def _map_dim(Y):
+    """Columns of a fitted map (numpy array or torch tensor): 2 or 3."""
+    if Y.ndim != 2 or Y.shape[1] not in (2, 3):
+        raise ValueError("the map must be n x 2 or n x 3, got shape %s" % (tuple(Y.shape),))
+    return int(Y.shape[1])
+
+
 def default_params(**kw):
     p = Params()
     lib().tsne_params_default(C.byref(p))
@@ -331,41 +338,57 @@ class Context:
 
     def repulsionQueries(self, Y, theta, Q):
         """tsne_repulsion_queries: computeRepulsiveForce of the tree of Y for the
-        points Q, which are not in it -> (F[m, 2], z[m]) in the order of Q."""
+        points Q, which are not in it -> (F[m, c], z[m]) in the order of Q.  A
+        3-column Y takes its octree (tsne_repulsion_queries_c)."""
         Y, Q = _f64(Y), _f64(Q)
-        if Y.ndim != 2 or Y.shape[1] != 2 or Q.ndim != 2 or Q.shape[1] != 2:
-            raise ValueError("Y and Q must be n x 2 and m x 2")
+        c = _map_dim(Y)
+        if Q.ndim != 2 or Q.shape[1] != c:
+            raise ValueError("Y and Q must be n x %d and m x %d" % (c, c))
         m = Q.shape[0]
-        F = np.zeros((m, 2))
+        F = np.zeros((m, c))
         z = np.zeros(m)
-        check(lib().tsne_repulsion_queries(self._h, _ptr(Y), Y.shape[0], theta, _ptr(Q), m, _ptr(F), _ptr(z)))
+        if c == 2:
+            check(lib().tsne_repulsion_queries(self._h, _ptr(Y), Y.shape[0], theta, _ptr(Q), m, _ptr(F), _ptr(z)))
+        else:
+            check(lib().tsne_repulsion_queries_c(self._h, _ptr(Y), Y.shape[0], c, theta, _ptr(Q), m, _ptr(F),
+                                                 _ptr(z)))
         return F, z
 
     def transformInit(self, row_ptr, col, P, Y_ref):
         """tsne_transform_init: the P-weighted mean of each new point's neighbours
-        on the map -> Y[m, 2]."""
+        on the map -> Y[m, c], c = 2 or 3 the columns of Y_ref."""
         Y_ref = _f64(Y_ref)
+        c = _map_dim(Y_ref)
         m = len(row_ptr) - 1
         rp, cl, pv = _csr(row_ptr, col, P, m)   # converted copies stay referenced across the call
-        Y = np.zeros((m, 2))
-        check(lib().tsne_transform_init(self._h, _ptr(rp), _ptr(cl), _ptr(pv), m, _ptr(Y_ref), Y_ref.shape[0],
-                                        _ptr(Y)))
+        Y = np.zeros((m, c))
+        if c == 2:
+            check(lib().tsne_transform_init(self._h, _ptr(rp), _ptr(cl), _ptr(pv), m, _ptr(Y_ref), Y_ref.shape[0],
+                                            _ptr(Y)))
+        else:
+            check(lib().tsne_transform_init_c(self._h, _ptr(rp), _ptr(cl), _ptr(pv), m, _ptr(Y_ref), Y_ref.shape[0],
+                                              c, _ptr(Y)))
         return Y
 
     def transform(self, Y_ref, row_ptr, col, P, Y, upd, gains, params):
         """tsne_transform: params.iterations iterations that move only the new
-        points, in place on Y / upd / gains (m x 2); returns {iteration: loss}."""
+        points, in place on Y / upd / gains (m x c, c = 2 or 3 the columns of
+        Y_ref; a 3-column map takes tsne_transform_c and needs
+        params.n_components == 3); returns {iteration: loss}."""
         Y_ref = _f64(Y_ref)
+        c = _map_dim(Y_ref)
         m = Y.shape[0]
-        _inout(m, 2, Y=Y, upd=upd, gains=gains)   # written in place by the library
+        _inout(m, c, Y=Y, upd=upd, gains=gains)   # written in place by the library
+        if c == 3 and params.n_components != 3:
+            raise ValueError("Y_ref has 3 columns, params.n_components is %d" % params.n_components)
         rp, cl, pv = _csr(row_ptr, col, P, m)
         cap = params.iterations // 10 + 1
         keys = np.zeros(cap, dtype=np.int32)
         vals = np.zeros(cap)
         nl = C.c_int32()
-        check(lib().tsne_transform(self._h, C.byref(params), _ptr(Y_ref), Y_ref.shape[0], _ptr(rp), _ptr(cl),
-                                   _ptr(pv), m, _ptr(Y), _ptr(upd), _ptr(gains), _ptr(keys), _ptr(vals), cap,
-                                   C.byref(nl)))
+        fn = lib().tsne_transform if c == 2 else lib().tsne_transform_c
+        check(fn(self._h, C.byref(params), _ptr(Y_ref), Y_ref.shape[0], _ptr(rp), _ptr(cl), _ptr(pv), m, _ptr(Y),
+                 _ptr(upd), _ptr(gains), _ptr(keys), _ptr(vals), cap, C.byref(nl)))
         k = min(nl.value, cap)
         return dict(zip(keys[:k].tolist(), vals[:k].tolist()))
 
@@ -378,15 +401,29 @@ class Context:
 
     def dev_repulsion_queries(self, dY, theta, dQ, dF, dz):
         self._fence(dY)
-        check(lib().tsne_dev_repulsion_queries(self._h, _ptr(dY), dY.shape[0], theta, _ptr(dQ), dQ.shape[0],
-                                               _ptr(dF), _ptr(dz)))
+        c = _map_dim(dY)
+        if dQ.ndim != 2 or dQ.shape[1] != c or tuple(dF.shape) != tuple(dQ.shape):
+            raise ValueError("dQ and dF must be m x %d" % c)
+        if c == 2:
+            check(lib().tsne_dev_repulsion_queries(self._h, _ptr(dY), dY.shape[0], theta, _ptr(dQ), dQ.shape[0],
+                                                   _ptr(dF), _ptr(dz)))
+        else:
+            check(lib().tsne_dev_repulsion_queries_c(self._h, _ptr(dY), dY.shape[0], c, theta, _ptr(dQ), dQ.shape[0],
+                                                     _ptr(dF), _ptr(dz)))
 
     def dev_transform_setup(self, params, dY_ref, d_row_ptr, d_col, d_P, dY, dupd, dgains):
-        """The tensors are used in place until the last step: keep them alive."""
+        """The tensors are used in place until the last step: keep them alive.
+        A 3-column map takes tsne_dev_transform_setup_c (params.n_components == 3)."""
         self._fence(dY)
-        check(lib().tsne_dev_transform_setup(self._h, C.byref(params), _ptr(dY_ref), dY_ref.shape[0],
-                                             _ptr(d_row_ptr), _ptr(d_col), _ptr(d_P), dY.shape[0], _ptr(dY),
-                                             _ptr(dupd), _ptr(dgains)))
+        c = _map_dim(dY_ref)
+        for name, a in (("dY", dY), ("dupd", dupd), ("dgains", dgains)):
+            if a.ndim != 2 or a.shape[1] != c or a.shape[0] != dY.shape[0]:
+                raise ValueError("%s must be m x %d" % (name, c))
+        if c == 3 and params.n_components != 3:
+            raise ValueError("dY_ref has 3 columns, params.n_components is %d" % params.n_components)
+        fn = lib().tsne_dev_transform_setup if c == 2 else lib().tsne_dev_transform_setup_c
+        check(fn(self._h, C.byref(params), _ptr(dY_ref), dY_ref.shape[0], _ptr(d_row_ptr), _ptr(d_col), _ptr(d_P),
+                 dY.shape[0], _ptr(dY), _ptr(dupd), _ptr(dgains)))
 
     def dev_transform_step(self, t):
         check(lib().tsne_dev_transform_step(self._h, t))
@@ -481,18 +518,19 @@ def transform(ctx, X_ref, Y_ref, X_new, k, perplexity, metric="sqeuclidean", par
     """Embed the rows of X_new into the fitted map Y_ref of X_ref, which stays
     fixed: cross kNN -> pairwiseAffinities on the cross distances (conditional
     p_{j|i}, not symmetrised) -> transformInit -> Context.transform.
-    Returns (Y_new[m, 2], {iteration: loss}).
+    Returns (Y_new[m, c], {iteration: loss}), c = 2 or 3 the columns of Y_ref.
 
     params: default_params() with learning_rate = 1.0, NOT the fit's 1000 -- every
     new point is normalised by its own z_i, so its gradient is of order 1.  On
     the 2000-point test map (tests/test_gpu_transform.py) 1.0 was stable and 10
     diverged (max |Y| 46 -> 637); nothing else has been tuned."""
     X_ref, Y_ref, X_new = _f64(X_ref), _f64(Y_ref), _f64(X_new)
+    c = _map_dim(Y_ref)
     if params is None:
-        params = default_params(learning_rate=1.0, metric=metric)
+        params = default_params(learning_rate=1.0, n_components=c, metric=metric)
     m = X_new.shape[0]
     if m == 0:
-        return np.zeros((0, 2)), {}
+        return np.zeros((0, c)), {}
     idx, dist = ctx.kNearestNeighborsCross(X_ref, X_new, k, metric)
     kk = idx.shape[1]
     rp = np.arange(0, m * kk + 1, kk, dtype=np.int64)
