@@ -1,4 +1,4 @@
-"""Embedding new points into a fitted 3-D map (csrc/transform3.hip): the
+"""Embedding new points into a fitted 3-D map (csrc/transform.hip): the
 octree walk for query points that are not in the tree, and the optimizer that
 moves only the new points.  Section by section the 3-D form of
 test_gpu_transform.py, against the oracle's octree restatement
@@ -13,7 +13,7 @@ ties: the octree has 21 levels per axis, a level-21 cell is about 1e-6 of the
 extent, and no two distinct reference points are closer than 1e-5 of it (in
 the Chebyshev distance); a tie group follows the library's documented
 approximation, not the oracle.  Exact duplicates are counted as the oracle
-counts them (the re-insert-once rule, transform3.hip dup_fix3).
+counts them (the re-insert-once rule, transform.hip dup_fix3).
 
 A transform step: the gradient error is <= 3e-11 (the bound above through
 rep / z with |rep / z| <= 1/2 gives 2e-11, plus the k-term attraction), so

@@ -449,7 +449,7 @@ int tsne_ctx_counter(tsne_ctx *ctx, const char *name, int64_t *value_out) {
         else if (k == "opt.stream_lists")
             *value_out = opt_tree(ctx) ? bh_stream_counter(ctx, *opt_tree(ctx)) : 0;
         else if (k.rfind("bh.", 0) == 0 && repulsion_stat(ctx, k, value_out)) {}
-        else if (k == "xform3.pops") *value_out = transform3_pops(ctx);
+        else if (k == "xform3.pops") *value_out = transform_pops(ctx);
         else if (k == "comm.kind") *value_out = comm_counter(ctx, false);
         else if (k == "comm.calls") *value_out = comm_counter(ctx, true);
         else if (k == "opt.csort_oversized") *value_out = opt_tree(ctx) ? csort_oversized(ctx, opt_tree(ctx)->cs) : 0;
@@ -1004,8 +1004,8 @@ int tsne_dev_knn_cross(tsne_ctx *ctx, const double *dX, int64_t n, const double 
 }
 
 // The operators below for a map of dimension c (2: the quadtree path of
-// transform.hip, 3: the octree path of transform3.hip); the entry points
-// without a suffix pass c = 2.
+// transform.hip, 3: its octree path); the entry points without a suffix pass
+// c = 2.
 static void check_map_dim(int32_t c) {
     if (c != 2 && c != 3) fail(TSNE_ERR_UNSUPPORTED, "the map's dimension must be 2 or 3");
 }
@@ -1024,11 +1024,10 @@ static int repulsion_queries_host(tsne_ctx *ctx, const double *Y, int64_t n, int
         double *dQ = upload(ctx, "h.Q", Q, (size_t)m * c);
         double *dF = ctx->ws.get<double>("h.qF", (size_t)m * c);
         double *dz = ctx->ws.get<double>("h.qz", (size_t)m);
-        if (c == 3) repulsion_queries3_device(ctx, dY, n, theta, dQ, m, dF, dz);
-        else repulsion_queries_device(ctx, dY, n, theta, dQ, m, dF, dz);
+        repulsion_queries_device(ctx, dY, n, c, theta, dQ, m, dF, dz);
         download(ctx, F_out, dF, (size_t)m * c);
         download(ctx, z_out, dz, (size_t)m);
-        walk_flag_check(ctx, c == 3 ? "octx1." : "bhx1.");
+        walk_flag_check(ctx, c);
     });
 }
 
@@ -1055,8 +1054,7 @@ int tsne_dev_repulsion_queries_c(tsne_ctx *ctx, const double *dY, int64_t n, int
         DeviceGuard g(ctx->device);
         check_map_dim(c);
         TSNE_REQUIRE(m == 0 || (dY && dQ && d_F && d_z), "NULL buffer");
-        if (c == 3) repulsion_queries3_device(ctx, dY, n, theta, dQ, m, d_F, d_z);
-        else repulsion_queries_device(ctx, dY, n, theta, dQ, m, d_F, d_z);
+        repulsion_queries_device(ctx, dY, n, c, theta, dQ, m, d_F, d_z);
     });
 }
 
@@ -1082,8 +1080,7 @@ int tsne_transform_init_c(tsne_ctx *ctx, const int64_t *row_ptr, const int32_t *
         double *dp = upload(ctx, "h.xp", P, (size_t)nnz);
         double *dYr = upload(ctx, "h.xYref", Yref, (size_t)n * c);
         double *dY = ctx->ws.get<double>("h.xY", (size_t)m * c);
-        if (c == 3) transform_init3_device(ctx, drp, dc, dp, m, dYr, n, dY);
-        else transform_init_device(ctx, drp, dc, dp, m, dYr, n, dY);
+        transform_init_device(ctx, drp, dc, dp, m, dYr, n, c, dY);
         download(ctx, Y_out, dY, (size_t)m * c);
         sync(ctx);
     });
@@ -1098,11 +1095,7 @@ static int transform_host(tsne_ctx *ctx, const tsne_params *params, const double
         check_ctx(ctx);
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
-        TSNE_REQUIRE(params != nullptr, "params is NULL");
-        if (!allow3 && params->n_components != 2)
-            fail(TSNE_ERR_UNSUPPORTED, "the transform is 2-D only (n_components must be 2)");
-        check_map_dim(params->n_components);
-        const size_t c = (size_t)params->n_components;
+        const size_t c = (size_t)transform_dim(params, allow3);
         TSNE_REQUIRE(m >= 0 && n >= 1, "bad sizes");
         if (n_loss) *n_loss = 0;
         if (m == 0) return;

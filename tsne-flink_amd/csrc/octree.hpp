@@ -66,7 +66,7 @@ __device__ __forceinline__ bool quant21(double p, double W, uint32_t &q) {
 
 // The octree's key of point (px, py, pz) in the root cell (0, 0, 0, W): one
 // device function for morton3_keys (octree.hip) and the transform's query sort
-// (transform3.hip).  Digit c = 4 lower + 2 south + east, tried in ascending c
+// (transform.hip).  Digit c = 4 lower + 2 south + east, tried in ascending c
 // (the child order).
 __device__ __forceinline__ uint64_t morton3_key(double px, double py, double pz, double W) {
     double x = 0.0, y = 0.0, z = 0.0, h = W;
@@ -116,7 +116,7 @@ struct OctTree {
     double4 *pos = nullptr;                          // sorted positions (x, y, z, 0)
     OctNode *nodes = nullptr;
     ORec *orec = nullptr;                            // per binary node id, valid for real cells
-    ORec *vrec = nullptr;                            // transform3.hip's duplicate fix-up: virtual chain-top records
+    ORec *vrec = nullptr;                            // transform.hip's duplicate fix-up: virtual chain-top records
                                                      // (ref n + node id); null without exact duplicates
     double near_dmax = 0.0;                          // the records' near-exact radius (this build)
     double *agg = nullptr;
@@ -142,7 +142,7 @@ struct OctTree {
 // Allocate (from ctx->ws, buffers named pre + field) for n points: the
 // optimizer's tree "oct.", the single-call operators' "oct1." (the coherent
 // sort reads the previous build's order, so two trees never share buffers).
-// records_only: a tree for the transform's foreign walk (transform3.hip),
+// records_only: a tree for the transform's foreign walk (transform.hip),
 // which reads the octal records and no subtree moments -- the moment and
 // moment-task buffers are not allocated, and such a tree serves oct_build
 // (records_only) alone, not oct_repulsion.

@@ -1,7 +1,7 @@
 // transform.hpp -- embedding new points into a fitted map: Barnes-Hut
 // repulsion for query points that are not in the tree, and the optimizer that
-// moves only the new points (transform.hip for 2-D maps, transform3.hip for
-// 3-D ones).
+// moves only the new points, for 2-D maps (the quadtree) and 3-D maps (the
+// octree): transform.hip.
 #pragma once
 #include "bhtree.hpp"
 #include "octree.hpp"
@@ -33,14 +33,17 @@ struct TransformState {
 };
 
 // computeRepulsiveForce (QuadTree.scala:123-152) of the tree of the n points
-// of dY for the m foreign points dQ: dF (m x 2) and dz (m), caller's order.
-void repulsion_queries_device(tsne_ctx *ctx, const double *dY, int64_t n, double theta, const double *dQ, int64_t m,
-                              double *dF, double *dz);
-// y_i = sum_e P_e Yref[col_e], sequential in CSR order (separate multiply and add)
+// of dY (n x c, c = 2: the quadtree, 3: the octree) for the m foreign points
+// dQ: dF (m x c) and dz (m), caller's order.
+void repulsion_queries_device(tsne_ctx *ctx, const double *dY, int64_t n, int32_t c, double theta, const double *dQ,
+                              int64_t m, double *dF, double *dz);
+// y_i = sum_e P_e Yref[col_e] (rows of c), sequential in CSR order (separate multiply and add)
 void transform_init_device(tsne_ctx *ctx, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_P,
-                           int64_t m, const double *d_Yref, int64_t n, double *d_Y);
-// allow3: params->n_components == 3 sets up the 3-D transform (the _c entry
-// points); otherwise it is TSNE_ERR_UNSUPPORTED, as any other value always is
+                           int64_t m, const double *d_Yref, int64_t n, int32_t c, double *d_Y);
+// The map's dimension of a transform, params->n_components.  allow3 (the _c
+// entry points): 3 is the 3-D transform; otherwise it is
+// TSNE_ERR_UNSUPPORTED, as any value but 2 and 3 always is.
+int32_t transform_dim(const tsne_params *p, bool allow3);
 void transform_setup(tsne_ctx *ctx, const tsne_params *p, const double *d_Yref, int64_t n,
                      const int64_t *d_row_ptr, const int32_t *d_col, const double *d_P, int64_t m, double *d_Y,
                      double *d_upd, double *d_gains, bool allow3 = false);
@@ -48,27 +51,11 @@ void transform_step(tsne_ctx *ctx, int32_t t);
 void transform_sync(tsne_ctx *ctx);
 int32_t transform_losses(tsne_ctx *ctx, int32_t *keys, double *vals, int32_t cap);
 void transform_destroy(tsne_ctx *ctx);   // the transform state and tsne_repulsion_queries[_c]'s trees
-// The flag word of the walks on the tree with workspace prefix `pre`, cleared
-int32_t *walk_flag(tsne_ctx *ctx, const std::string &pre);
-// Fails (TSNE_ERR_HIP) if a walk on the tree with workspace prefix `pre`
-// ("bhx." / "bhx1." / "octx." / "octx1.") met a full stack since its flag was
-// cleared; synchronises.
-void walk_flag_check(tsne_ctx *ctx, const char *pre);
-
-// ---- 3-D maps (transform3.hip): the same operators over the octree of dY /
-// d_Yref (n x 3); F, Y, upd, gains are m x 3.
-void repulsion_queries3_device(tsne_ctx *ctx, const double *dY, int64_t n, double theta, const double *dQ, int64_t m,
-                               double *dF, double *dz);
-void transform_init3_device(tsne_ctx *ctx, const int64_t *d_row_ptr, const int32_t *d_col, const double *d_P,
-                            int64_t m, const double *d_Yref, int64_t n, double *d_Y);
-// the pieces transform_setup / transform_step dispatch to when s->dim == 3:
-// the tree of s->Yref with the flag and the first sort; the Morton sort of
-// s->Y; the launches of one iteration (fused, or split under transform_split)
-void transform3_build(tsne_ctx *ctx, TransformState *s);
-void transform3_sort(tsne_ctx *ctx, TransformState *s);
-void transform3_launch(tsne_ctx *ctx, TransformState *s, double ex, double mom, bool loss);
-// wave pops of the last repulsion_queries3_device walk run under option
-// transform_stats (tsne_ctx_counter "xform3.pops"; 0 if none); synchronises
-int64_t transform3_pops(tsne_ctx *ctx);
+// Fails (TSNE_ERR_HIP) if a walk of repulsion_queries_device on the tree of a
+// c-dimensional map met a full stack since its flag was cleared; synchronises.
+void walk_flag_check(tsne_ctx *ctx, int32_t c);
+// wave pops of the last repulsion_queries_device walk of a 3-D map run under
+// option transform_stats (tsne_ctx_counter "xform3.pops"; 0 if none); synchronises
+int64_t transform_pops(tsne_ctx *ctx);
 
 }  // namespace tsne
