@@ -216,6 +216,13 @@ int tsne_ctx_synchronize(tsne_ctx *ctx);
  *                             the subtree moments run on the second stream
  *                             beside the traversal; 0: one launch per pass
  *                             (the same arrays, bit for bit);
+ *   "tile_pass" 0             the tile sums' packed rounds (<= 64 points of
+ *                             consecutive small tiles): 1: each lane walks its
+ *                             tiles of a round as runs of staged points; 2, 4,
+ *                             8: over passes of that many consecutive rounds,
+ *                             staged together and walked in one loop; 0: the
+ *                             earlier slot-mask loops, a round at a time (the
+ *                             same sums, bit for bit, for every value);
  *   "transform_resort" 10     tsne_dev_transform_step: the new points are sorted
  *                             again by the map tree's Morton key every this
  *                             many steps (0: only at setup); changes no result,
@@ -277,6 +284,12 @@ int tsne_ctx_loop_profile(tsne_ctx *ctx, char *buf, int64_t cap, int64_t *len_ou
  *                        moment evaluations, and per dense path of tile_apply
  *                        (lane-wise, packed, query-major, staged sweep) the
  *                        wave steps issued and the useful lane pairs;
+ *   "bh.tile_gsteps<p>_<G>", p = 0 | 1, G = 2 | 4 | 8  (rep_stats, tile_pass <= 1)
+ *                        the wave steps that passes over G consecutive
+ *                        lane-wise windows (0) / packed rounds (1) would take;
+ *   "bh.tile_rounds_max", "bh.tile_chunked_waves"  (rep_stats) the most packed
+ *                        rounds of one tile_apply wave; the waves that are one
+ *                        chunk of a split tile list;
  *   "comm.kind"          the context's communicator: 0 none, 1 RCCL, 2 loopback,
  *                        3 caller callbacks; "comm.calls" collectives it issued;
  *   "opt.attract_kernel" the optimizer's attraction kernel: 0 attract_rows,

@@ -84,6 +84,14 @@ def main():
                           "slow_wave_tile_points", "slow_wave_slots", "wave_mhz") + tuple(f"tile_{w}{j}" for j in range(4)
                                                                               for w in ("steps", "pairs")):
                     rec[k] = ctx.counter("bh." + k)
+                if ctx_has_option(ctx, "tile_pass"):
+                    # what passes over G = 2, 4, 8 consecutive lane-wise windows (0) / packed rounds (1)
+                    # would cost in wave steps (counted with tile_pass <= 1), the most packed rounds of
+                    # one wave, the waves that are a chunk of a split tile list
+                    rec["tile_pass"] = ctx.get_option("tile_pass")
+                    for k in tuple(f"tile_gsteps{p}_{g}" for p in (0, 1) for g in (2, 4, 8)) + (
+                            "tile_rounds_max", "tile_chunked_waves"):
+                        rec[k] = ctx.counter("bh." + k)
                 ctx.set_option("rep_stats", 0)
             print(json.dumps(rec), flush=True)
 

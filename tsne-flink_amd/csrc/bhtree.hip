@@ -2860,23 +2860,47 @@ __global__ __launch_bounds__(1024) void trav_order_cur(const int32_t *__restrict
 // "Tile streaming"): persistent waves taking the handed-over lists, moments
 // recorded per consumer lane and evaluated after its tiles, F += D + M.  MODE 0 skips the
 // streamed waves' lists (st_streamed: their list length and tile cost).
-template <int MODE>
+//
+// The packed rounds (Options::tile_pass).  PASS 0: each round of <= 64 staged
+// points is swept by iterating the bits of the lane's 64-bit slot mask.
+// PASS 1: the lane walks its TILES of the round (the round's tile masks
+// transposed, as the lane-wise windows do) as runs of consecutive slots -- an
+// increment and a compare inside a run, the mask pop only at its end -- and
+// reads the next slot before it sums the current one.  PASS 2: a pass forms
+// up to `tpass` consecutive rounds (the same tiles per round, the same
+// <= 64-slot boundary), stages their points side by side and lets every lane
+// walk its runs through all of them in one divergent loop; a lane folds its
+// partial sums into (fx, fy, zs) and clears them each time it crosses from one
+// round to the next, so the sums are grouped as by the one-round loops: the
+// same bits for every value.  STATS: the counting instantiation (launched with
+// `visits`); the other one carries none of the counters.
+// Dynamic LDS per wave, for G = max(tpass, 1) rounds a pass (tile_lds_wave):
+// G x 64 staged points, G x 64 transposed tile masks (the lane-wise windows'
+// tile ranges share their space), G x 64 packed slot ranges, 64 slot marks.
+__host__ __device__ constexpr int tile_lds_wave(int G) { return G * (1024 + 512 + 256) + 256; }
+template <int MODE, int PASS, bool STATS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void tile_apply(
     const double2 *__restrict__ pos, const BHNode *__restrict__ nodes, const TileTask *__restrict__ ttask,
     const int32_t *__restrict__ ttask_n, int64_t g0, int64_t g1, const int32_t *__restrict__ qlist,
     int32_t *__restrict__ mom_flag, double mom_tol, int32_t *__restrict__ mtask, int32_t *__restrict__ mtask_n,
     double2 *__restrict__ F, double *__restrict__ Z, unsigned long long *__restrict__ visits,
     const int32_t *__restrict__ torder, ChunkView cv, const double *__restrict__ mom, SpillView sv,
-    StreamView stv, const int32_t *__restrict__ tcost) {
+    StreamView stv, const int32_t *__restrict__ tcost, int tpass) {
     constexpr bool PAGE = MODE == 1, STREAM = MODE == 2;
-    __shared__ double2 tbuf[4][64];
-    __shared__ int smark[4][64];
-    __shared__ int2 srng[4][64];
+    extern __shared__ __attribute__((aligned(16))) unsigned char tile_lds[];
     constexpr float LW_COST = 1.0f;   // lane-wise cost per point relative to a sweep slot (gathers, refills;
                                       // 1.6 before the lane-wise loop lost its accumulator copies, round 5)
     const int lane = lane_id(), w = threadIdx.x >> 6;
+    const int Gp = PASS == 2 ? tpass : 1;   // rounds a pass
+    unsigned char *const wlds = tile_lds + w * tile_lds_wave(Gp);
+    double2 *const buf = reinterpret_cast<double2 *>(wlds);                          // staged points
+    uint64_t *const wmk = reinterpret_cast<uint64_t *>(wlds + Gp * 1024);            // lane -> its tiles of round g
+    int2 *const srng = reinterpret_cast<int2 *>(wlds + Gp * 1024);                   // (lane-wise window: tile ranges)
+    uint32_t *const rngw = reinterpret_cast<uint32_t *>(wlds + Gp * 1536);           // tile -> first | last << 16 slot
+    int *const smark = reinterpret_cast<int *>(wlds + Gp * 1792);
     int64_t wid, qw;
     int tb, nt;
+    bool chunked = false;   // (STATS) this wave is one of several chunks of its tile list
     const TileTask *mytt;
     // PAGE: pages blockIdx.x * 4 + w, + 4 gridDim.x, ... (the loop's end below)
     for (int64_t pit = (int64_t)blockIdx.x * 4 + w;; pit += (int64_t)gridDim.x * 4) {
@@ -2928,6 +2952,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
             const int32_t v = cv.slot_c[wid];
             ch = v & 0xffff;
             C = v >> 16;
+            chunked = C > 1;
         }
         if (g0 + qw * 64 >= g1) return;
         mytt = ttask + qw * TILE_CAP;
@@ -2955,7 +2980,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
     double qx = 0.0, qy = 0.0;
     if (valid) { const double2 q = pos[s]; qx = q.x; qy = q.y; }
     const bool mom_on = mom_flag[0] != 0;
-    const unsigned long long w_start = visits ? wall_clock64() : 0;
+    const unsigned long long w_start = STATS ? wall_clock64() : 0;
     double fx = 0.0, fy = 0.0, zs = 0.0;
     int nwant = 0, ntask = 0;
     unsigned long long ndense = 0;
@@ -2963,7 +2988,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
     // per dense path (lane-wise, packed sweep, query-major, staged sweep): wave
     // steps (pair slots the wave issues) and this lane's useful pairs
     unsigned long long ps_steps[4] = {0, 0, 0, 0}, ps_pairs[4] = {0, 0, 0, 0};
-    double2 *buf = tbuf[w];
+    // (STATS, one round a pass) what passes over G = 2, 4, 8 consecutive packed
+    // rounds [0..2] / lane-wise windows [3..5] would cost: the wave maximum of
+    // each lane's steps summed over the G of them, a group ending where the
+    // wave leaves that path; and the wave's packed rounds
+    unsigned long long gsteps[6] = {0, 0, 0, 0, 0, 0};
+    int gacc[6] = {0, 0, 0, 0, 0, 0}, gcnt[6] = {0, 0, 0, 0, 0, 0}, nrounds = 0;
+    auto group_add = [&](int path, int mine) {   // one more round / window of `path` (1 packed, 0 lane-wise)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int i = (path ? 0 : 3) + k;
+            gacc[i] += mine;
+            if (++gcnt[i] == (2 << k)) { gsteps[i] += (unsigned long long)wave_max(gacc[i]); gacc[i] = 0; gcnt[i] = 0; }
+        }
+    };
+    auto group_end = [&](int path) {   // the wave leaves `path`: its open groups end here
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int i = (path ? 0 : 3) + k;
+            if (gcnt[i]) { gsteps[i] += (unsigned long long)wave_max(gacc[i]); gacc[i] = 0; gcnt[i] = 0; }
+        }
+    };
     int masked_until = tb;   // tiles before this one take the masked sweep
     for (int t = tb; t < nt;) {
         const TileTask tt = STREAM ? vec_load(mytt + t) : mytt[t];
@@ -3005,13 +3050,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
             // slot, gathers and refills included), the sweep for the whole window.
             const int cnt_i = b_i - a_i + 1;
             __builtin_amdgcn_wave_barrier();
-            srng[w][lane] = make_int2(a_i, b_i);
+            srng[lane] = make_int2(a_i, b_i);
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_wave_barrier();
             int cl = 0;
             for (uint64_t wb = W; wb; wb &= wb - 1) {
-                const int2 r = srng[w][__ffsll((long long)wb) - 1];
+                const int2 r = srng[__ffsll((long long)wb) - 1];
                 cl += r.y - r.x + 1;
             }
             const int cmax = wave_max(cl), ctot = wave_sum(lane < wn ? cnt_i : 0);
@@ -3027,7 +3072,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
             if (W) {
                 int i = __ffsll((long long)W) - 1;
                 W &= W - 1;
-                int2 r = srng[w][i];
+                int2 r = srng[i];
                 int p = r.x, last = r.y;
                 bool more;
                 do {
@@ -3036,23 +3081,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
                     const double2 p1 = pos[two ? p + 1 : p];
                     pair_force(qx, qy, p0.x, p0.y, ux, uy, uz);
                     pair_force_m(two, qx, qy, p1.x, p1.y, ux, uy, uz);
-                    nmine += two ? 2 : 1;
-                    ++nit;
+                    if (STATS) { nmine += two ? 2 : 1; ++nit; }
                     p += 2;
                     if (p > last && W) {
                         i = __ffsll((long long)W) - 1;
                         W &= W - 1;
-                        r = srng[w][i];
+                        r = srng[i];
                         p = r.x; last = r.y;
                     }
                     more = p <= last;
                 } while (more);
             }
-            if (visits) ps_steps[0] += 2ull * (unsigned long long)wave_max(nit);
+            if (STATS) ps_steps[0] += 2ull * (unsigned long long)wave_max(nit);
             __builtin_amdgcn_wave_barrier();
             fx += ux; fy += uy; zs += uz;
             ndense += (unsigned long long)nmine;
-            if (visits) {
+            if (STATS) {
+                group_end(1);
+                group_add(0, nit);
                 ps_pairs[0] += (unsigned long long)nmine;
                 wt_tasks += (unsigned long long)wn;
                 wt_dense_pts += (unsigned long long)wave_sum(lane < wn ? b_i - a_i + 1 : 0);
@@ -3067,6 +3113,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
             // (point, tile lane mask) and swept once, each lane taking the points
             // of its own tiles -- one staging round per <= 64 points instead of
             // one per tile (tiles average ~9 points in the mid phase).
+            if (STATS) group_end(0);
+            if constexpr (PASS == 0) {
             const int ti = t + lane;
             int c_i = 1 << 20, a_i = 0;
             uint64_t m_i = 0;
@@ -3084,13 +3132,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
             const int mtake = __popcll(__ballot(S <= 64));   // >= 1: tile t itself fits
             const int total = __shfl(S, mtake - 1, 64);
             __builtin_amdgcn_wave_barrier();
-            smark[w][lane] = -1;
+            smark[lane] = -1;
             __builtin_amdgcn_wave_barrier();
-            if (lane < mtake) smark[w][S - c_i] = lane;
+            if (lane < mtake) smark[S - c_i] = lane;
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_wave_barrier();
-            int own = smark[w][lane];   // slot -> tile: running max of the start markers
+            int own = smark[lane];   // slot -> tile: running max of the start markers
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
                 const int v = __shfl_up(own, o, 64);
@@ -3135,21 +3183,151 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
                     M &= M - 1;
                     const double2 pn = buf[j];
                     pair_force(qx, qy, pp.x, pp.y, ux, uy, uz);
-                    if (visits) ++nmine;
+                    if (STATS) ++nmine;
                     pp = pn;
                 } while (more);
             }
-            if (visits) ps_steps[1] += (unsigned long long)wave_max(nmine);
+            if (STATS) ps_steps[1] += (unsigned long long)wave_max(nmine);
             __builtin_amdgcn_wave_barrier();
             fx += ux; fy += uy; zs += uz;
             ndense += (unsigned long long)nmine;
-            if (visits) {
+            if (STATS) {
                 wt_tasks += (unsigned long long)mtake; wt_dense_pts += (unsigned long long)total;
                 ps_pairs[1] += (unsigned long long)nmine;
+                group_add(1, nmine);
+                ++nrounds;
             }
             t += mtake;
+            } else {
+            // A pass: up to Gp rounds, each formed as above (the tiles from t on
+            // whose points fit 64 slots), while the next tile is small, inside
+            // this chunk and before masked_until.  Round g's points go to slots
+            // g x 64 .. of the stage; they are loaded one round ahead of their
+            // LDS write (and the next round's tile headers before them), so a
+            // round's loads fly while the next one is formed.
+            int ng = 0, ntile_p = 0, npts_p = 0;
+            double2 pend = make_double2(0.0, 0.0);
+            // tile t + lane's range and mask, read unconditionally (past the
+            // chunk's end: its last tile again, then ignored) so that nothing
+            // but the loads themselves stands between their issue and their use
+            int hf, hl;
+            uint64_t hm;
+            { const TileTask &h = mytt[min(t + lane, nt - 1)]; hf = h.first; hl = h.last; hm = h.mask; }
+            for (;;) {
+                int c_i = hl - hf + 1, a_i = hf;
+                uint64_t m_i = hm;
+                if (t + lane >= nt || c_i >= MOM_MIN_POINTS) { c_i = 1 << 20; a_i = 0; m_i = 0; }
+                if (ng > 0 && __builtin_amdgcn_readfirstlane(c_i) == (1 << 20)) break;   // tile t is not small
+                int S = c_i;   // inclusive prefix of the counts
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int v = __shfl_up(S, o, 64);
+                    if (lane >= o) S += v;
+                }
+                const int mtake = __popcll(__ballot(S <= 64));   // >= 1: tile t itself fits
+                const int total = __shfl(S, mtake - 1, 64);
+                const int tn = t + mtake;
+                const bool cont = ng + 1 < Gp && tn < nt && tn < masked_until;
+                // the next round's tile headers (read even where the pass ends here)
+                { const TileTask &h = mytt[min(tn + lane, nt - 1)]; hf = h.first; hl = h.last; hm = h.mask; }
+                __builtin_amdgcn_wave_barrier();
+                smark[lane] = -1;
+                __builtin_amdgcn_wave_barrier();
+                if (lane < mtake) smark[S - c_i] = lane;
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_s_waitcnt(0xc07f);
+                __builtin_amdgcn_wave_barrier();
+                int own = smark[lane];   // slot -> tile: running max of the start markers
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int v = __shfl_up(own, o, 64);
+                    if (lane >= o) own = max(own, v);
+                }
+                const int st = __shfl(S - c_i, own, 64), fa = __shfl(a_i, own, 64);
+                if (ng > 0) buf[(ng - 1) * 64 + lane] = pend;
+                pend = pos[fa + (lane < total ? lane - st : 0)];   // (slots >= total: some point, never read)
+                // row i = tile t + i's lane mask, transposed: bit i of lane l = tile t + i is one of l's
+                uint64_t Wt = lane < mtake ? m_i : 0ull;
+#pragma unroll
+                for (int st2 = 0; st2 < 6; ++st2) {
+                    const int j = 32 >> st2;
+                    const uint64_t lo = st2 == 0 ? 0x00000000FFFFFFFFull : st2 == 1 ? 0x0000FFFF0000FFFFull
+                                      : st2 == 2 ? 0x00FF00FF00FF00FFull : st2 == 3 ? 0x0F0F0F0F0F0F0F0Full
+                                      : st2 == 4 ? 0x3333333333333333ull : 0x5555555555555555ull;
+                    const uint32_t ylo = __shfl_xor((uint32_t)Wt, j, 64), yhi = __shfl_xor((uint32_t)(Wt >> 32), j, 64);
+                    const uint64_t y = ((uint64_t)yhi << 32) | ylo;
+                    Wt = (lane & j) ? ((Wt & ~lo) | ((y & ~lo) >> j)) : ((Wt & lo) | ((y & lo) << j));
+                }
+                wmk[ng * 64 + lane] = Wt;
+                if (lane < mtake)
+                    rngw[ng * 64 + lane] = (uint32_t)(ng * 64 + S - c_i) | ((uint32_t)(ng * 64 + S - 1) << 16);
+                if (STATS) { ntile_p += mtake; npts_p += total; }
+                t = tn;
+                ++ng;
+                if (!cont) break;
+            }
+            buf[(ng - 1) * 64 + lane] = pend;
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            __builtin_amdgcn_wave_barrier();
+            double ux = 0.0, uy = 0.0, uz = 0.0;
+            int nmine = 0;
+            // a divergent do-while per lane over its runs (tile order, then slot
+            // order: the one-round loops' order), the next slot read before the
+            // current one is summed; the accumulators are updated in place
+            int g = 0;
+            uint64_t W = wmk[lane];
+            if (PASS == 2)
+                while (W == 0ull && g + 1 < ng) W = wmk[++g * 64 + lane];   // (rounds without a slot add +0.0: below)
+            if (W) {
+                uint32_t r = rngw[g * 64 + __ffsll((long long)W) - 1];
+                W &= W - 1;
+                int p = (int)(r & 0xffffu), last = (int)(r >> 16);
+                double2 pp = buf[p];
+                bool more;
+                do {
+                    bool cross = false;
+                    more = true;
+                    if (p < last) {
+                        ++p;
+                    } else {
+                        if (PASS == 2)
+                            while (W == 0ull && g + 1 < ng) { W = wmk[++g * 64 + lane]; cross = true; }
+                        if (W) {
+                            r = rngw[g * 64 + __ffsll((long long)W) - 1];
+                            W &= W - 1;
+                            p = (int)(r & 0xffffu); last = (int)(r >> 16);
+                        } else {
+                            more = false;   // (p stays: the read below is discarded)
+                        }
+                    }
+                    const double2 pn = buf[p];
+                    pair_force(qx, qy, pp.x, pp.y, ux, uy, uz);
+                    if (STATS) ++nmine;
+                    if (PASS == 2 && cross) {   // the old round's boundary: its partial sums folded, as its own loop did
+                        fx += ux; fy += uy; zs += uz;
+                        ux = 0.0; uy = 0.0; uz = 0.0;
+                    }
+                    pp = pn;
+                } while (more);
+            }
+            __builtin_amdgcn_wave_barrier();
+            // the last round's fold; a lane that left rounds behind without a
+            // slot adds their +0.0 here (x + 0.0 = x for every sum these take:
+            // none is ever -0.0, being sums that started from +0.0)
+            fx += ux; fy += uy; zs += uz;
+            if (STATS) {
+                ps_steps[1] += (unsigned long long)wave_max(nmine);
+                ndense += (unsigned long long)nmine;
+                wt_tasks += (unsigned long long)ntile_p; wt_dense_pts += (unsigned long long)npts_p;
+                ps_pairs[1] += (unsigned long long)nmine;
+                nrounds += ng;
+                if (PASS == 1) group_add(1, nmine);
+            }
+            }
             continue;
         }
+        if (STATS) { group_end(0); group_end(1); }
         ++t;
         const int ref = __builtin_amdgcn_readfirstlane(tt.ref);
         const int a = __builtin_amdgcn_readfirstlane(tt.first), b = __builtin_amdgcn_readfirstlane(tt.last);
@@ -3176,7 +3354,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
         const bool dense = mine && !usem;
         const uint64_t dm = __ballot(dense);
         const int kq = __popcll(dm), cnt_t = b - a + 1;
-        if (visits) {
+        if (STATS) {
             ++wt_tasks;
             if (dm) wt_dense_pts += (unsigned long long)cnt_t;
             if (cnt >= MOM_MIN_POINTS && (tt.mask != 0)) ++wt_momchk;
@@ -3204,7 +3382,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
                 }
                 ux = wave_sum(ux); uy = wave_sum(uy); uz = wave_sum(uz);
                 if (lane == j) { fx += ux; fy += uy; zs += uz; ndense += (unsigned long long)cnt_t; }
-                if (visits) {
+                if (STATS) {
                     ps_steps[2] += (unsigned long long)((cnt_t + 63) / 64 + 6);
                     if (lane == j) ps_pairs[2] += (unsigned long long)cnt_t;
                 }
@@ -3236,7 +3414,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
             }
             __builtin_amdgcn_wave_barrier();
             if (dense) { fx += ux; fy += uy; zs += uz; ndense += (unsigned long long)(b - a + 1); }
-            if (visits) {
+            if (STATS) {
                 ps_steps[3] += (unsigned long long)(b - a + 1);
                 if (dense) ps_pairs[3] += (unsigned long long)(b - a + 1);
             }
@@ -3266,18 +3444,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
     // per wave on one word would serialise ~n / 64 of them)
     if (lane == 0 && wwant && __hip_atomic_load(&mom_flag[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < mom_flag[2])
         atomicAdd(&mom_flag[1], wwant);
-    if (visits) {   // [1] moment evaluations, [2] dense pair terms; [10..12] diagnostics:
+    if (STATS) {   // [1] moment evaluations, [2] dense pair terms; [10..12] diagnostics:
                     // tile tasks, wave-level dense points, tasks with a moment check
         const unsigned long long tm = wave_sum((unsigned long long)ntask), td = wave_sum(ndense);
         unsigned long long pp[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) pp[k] = wave_sum(ps_pairs[k]);
+        group_end(0); group_end(1);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {   // [24 + 2k] wave steps, [25 + 2k] lane pairs of dense path k
                 atomicAdd(visits + 24 + 2 * k, ps_steps[k]);
                 atomicAdd(visits + 25 + 2 * k, pp[k]);
             }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {   // [38 + k] packed, [41 + k] lane-wise: passes over 2, 4, 8 (PASS < 2)
+                atomicAdd(visits + 38 + k, gsteps[k]);
+                atomicAdd(visits + 41 + k, 2ull * gsteps[3 + k]);
+            }
+            atomicMax(visits + 44, (unsigned long long)nrounds);   // most packed rounds in one wave
+            if (chunked) atomicAdd(visits + 45, 1ull);             // waves that are a chunk of a split list
             atomicAdd(visits + 10, wt_tasks);
             atomicAdd(visits + 11, wt_dense_pts);
             atomicAdd(visits + 12, wt_momchk);
@@ -3293,6 +3479,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
     }
     if (MODE == 0) break;
     }
+}
+
+// tile_apply<MODE> for Options::tile_pass (0: the slot-bit loops; 1: one round a
+// pass; 2, 4, 8: that many -- the pages and the streaming consumers, whose
+// lists are short, stay at one) and with or without the counters.
+template <int MODE, class... Args>
+static void tile_apply_launch(int tile_pass, bool stats, dim3 grid, hipStream_t st, Args... args) {
+    const int pass = tile_pass == 0 ? 0 : tile_pass == 1 || MODE != 0 ? 1 : 2;
+    const int G = pass == 2 ? tile_pass : 1;
+    const size_t lds = 4 * (size_t)tile_lds_wave(G);
+#define TSNE_TILE_APPLY(P, S) hipLaunchKernelGGL((tile_apply<MODE, P, S>), grid, dim3(256), lds, st, args..., G)
+    if (pass == 0) { if (stats) TSNE_TILE_APPLY(0, true); else TSNE_TILE_APPLY(0, false); }
+    else if (pass == 1) { if (stats) TSNE_TILE_APPLY(1, true); else TSNE_TILE_APPLY(1, false); }
+    else if constexpr (MODE == 0) { if (stats) TSNE_TILE_APPLY(2, true); else TSNE_TILE_APPLY(2, false); }
+#undef TSNE_TILE_APPLY
 }
 
 // Tile streaming's last step (see "Tile streaming"), on the consumers' stream
@@ -4239,9 +4440,9 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
         ChunkView scv;
         scv.Fp = t.st_Dp;
         scv.Zp = t.st_Dz;
-        hipLaunchKernelGGL(tile_apply<2>, dim3(cblocks), dim3(256), 0, ctx->st_stream, t.pos, t.nodes, t.ttask,
-                           t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.st_mtask, t.st_mtask_n, dF, dz, visits,
-                           nullptr, scv, t.mom, SpillView(), stv, t.tcost);
+        tile_apply_launch<2>(o.tile_pass, visits != nullptr, dim3(cblocks), ctx->st_stream, t.pos, t.nodes, t.ttask,
+                             t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.st_mtask, t.st_mtask_n, dF, dz, visits,
+                             (const int32_t *)nullptr, scv, t.mom, SpillView(), stv, t.tcost);
         // (F, Z of the traversal itself: read after its launch has ended)
         TSNE_HIP(hipEventRecord(ctx->st_ev[2], st));
         TSNE_HIP(hipStreamWaitEvent(ctx->st_stream, ctx->st_ev[2], 0));
@@ -4289,9 +4490,9 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
     cv.slot_w = t.ch_slot_w; cv.slot_c = t.ch_slot_c; cv.nslots = t.ch_nslots;
     cv.Fp = t.ch_Fp; cv.Zp = t.ch_Zp;
     if (mom_late) TSNE_HIP(hipStreamWaitEvent(st, t.mom_ev, 0));   // t.mom: read from here on
-    hipLaunchKernelGGL(tile_apply<0>, dim3(ceil_div(tslots, 4)), dim3(256), 0, st, t.pos, t.nodes, t.ttask,
-                       t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.mtask, t.mtask_n, dF, dz, visits, torder, cv,
-                       t.mom, SpillView(), stv, t.tcost);
+    tile_apply_launch<0>(o.tile_pass, visits != nullptr, dim3(ceil_div(tslots, 4)), st, t.pos, t.nodes, t.ttask,
+                         t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.mtask, t.mtask_n, dF, dz, visits, torder, cv,
+                         t.mom, SpillView(), stv, t.tcost);
     hipLaunchKernelGGL(moment_apply, dim3(ceil_div(tslots * 64, 256)), dim3(256), 0, st, t.pos, t.nodes, t.mom,
                        t.mtask, t.mtask_n, s0, s1, qlist, dF, dz, cv);
     const bool keep_pcost = o.trav_front_cur > 0.0 && !plim && !qlist && s0 == 0 && s1 == t.n;
@@ -4305,9 +4506,9 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
                        narrow ? t.nflag : nullptr);
     t.pcost_valid = keep_pcost;
     if (spill) {   // the tasks' tile pages, then their sums into F, Z
-        hipLaunchKernelGGL(tile_apply<1>, dim3(std::max(1, ctx->cu_count * 4)), dim3(256), 0, st, t.pos, t.nodes,
-                           t.ttask, t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.mtask, t.mtask_n, dF, dz, visits,
-                           nullptr, ChunkView(), t.mom, sv, StreamView(), t.tcost);
+        tile_apply_launch<1>(o.tile_pass, visits != nullptr, dim3(std::max(1, ctx->cu_count * 4)), st, t.pos, t.nodes,
+                             t.ttask, t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.mtask, t.mtask_n, dF, dz, visits,
+                             (const int32_t *)nullptr, ChunkView(), t.mom, sv, StreamView(), t.tcost);
         hipLaunchKernelGGL(spill_combine, dim3(ceil_div(s1 - s0, 256)), dim3(256), 0, st, t.sp_gflag, t.sp_gen,
                            t.sp_acc, s0, s1, qlist, dF, dz, t.sp_ctl);
     }

@@ -155,6 +155,7 @@ static const OptionField k_options[] = {
     {"bu_acqrel", nullptr, &Options::bu_acqrel, 0, 1},
     {"bh_split", nullptr, &Options::bh_split, 0, 1},
     {"build_fuse", nullptr, &Options::build_fuse, 0, 1},
+    {"tile_pass", nullptr, &Options::tile_pass, 0, 8},
     {"transform_resort", nullptr, &Options::transform_resort, 0, 1 << 30},
     {"transform_split", nullptr, &Options::transform_split, 0, 1},
     {"transform_stats", nullptr, &Options::transform_stats, 0, 1},
@@ -170,6 +171,7 @@ static void set_option(Options &o, const char *key, double v) {
     if (f.d) o.*f.d = v;
     else {
         TSNE_REQUIRE(v == std::floor(v), std::string("option '") + key + "' takes an integer");
+        TSNE_REQUIRE(f.i != &Options::tile_pass || v <= 2 || v == 4 || v == 8, "option 'tile_pass' takes 0, 1, 2, 4 or 8");
         o.*f.i = (int)v;
     }
 }

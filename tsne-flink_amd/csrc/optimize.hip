@@ -1868,6 +1868,14 @@ bool repulsion_stat(tsne_ctx *ctx, const std::string &name, int64_t *value_out) 
     int atk = at;
     if (at < 0 && name.size() == 14 && name.compare(0, 13, "bh.tile_steps") == 0) atk = 24 + 2 * (name[13] - '0');
     if (at < 0 && name.size() == 14 && name.compare(0, 13, "bh.tile_pairs") == 0) atk = 25 + 2 * (name[13] - '0');
+    // "bh.tile_gsteps<p>_<G>": the wave steps passes over G = 2, 4, 8 consecutive lane-wise windows (p = 0) or
+    // packed rounds (p = 1) would take (counted with tile_pass <= 1); "bh.tile_rounds_max": the most packed
+    // rounds of one wave; "bh.tile_chunked_waves": tile_apply waves that are one chunk of a split list
+    if (at < 0 && name.size() == 17 && name.compare(0, 14, "bh.tile_gsteps") == 0 && name[15] == '_' &&
+        (name[14] == '0' || name[14] == '1') && (name[16] == '2' || name[16] == '4' || name[16] == '8'))
+        atk = (name[14] == '1' ? 38 : 41) + (name[16] == '2' ? 0 : name[16] == '4' ? 1 : 2);
+    if (name == "bh.tile_rounds_max") atk = 44;
+    if (name == "bh.tile_chunked_waves") atk = 45;
     if (atk < 0 || atk >= VIS_N) return false;
     TSNE_REQUIRE(ctx->opts.rep_stats && ctx->ws.has("rep.visits"), "counter '" + name + "' needs option rep_stats");
     unsigned long long v[VIS_N];
