@@ -210,7 +210,7 @@ def test_gradient_large_near_exact(ctx, n, scale):
 
 @pytest.mark.parametrize("n,scale,dups", [(20000, 1e-4, False), (5000, 1e-3, False), (5000, 1e-4, True)])
 def test_root_tile_mode_per_point(ctx, n, scale, dups):
-    """Root-tile mode (bhtree.hip: a small embedding's whole tree is one
+    """Root-tile mode (bhtree_build.hip: a small embedding's whole tree is one
     near-exact subtree for every query -> the root's moments as polynomials,
     no sort / tree): per-point F and z against the oracle's quadtree.  With
     exact duplicates the hash-round check sends the build to the full path

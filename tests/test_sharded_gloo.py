@@ -140,7 +140,7 @@ def test_sharded_iteration_matches_single_process(tmp_path, world):
 
 
 def test_balance_cuts_rule():
-    """tsne_balance_cuts (host mirror of the device rule in bhtree.hip)."""
+    """tsne_balance_cuts (host mirror of the device rule in bhpart.hip)."""
     import tsne_amd as TA
     assert TA.balance_cuts([0, 0, 0, 0], 1000, 4).tolist() == [0, 250, 500, 750, 1000]
     assert TA.balance_cuts([1, 1, 1, 1], 1000, 2).tolist() == [0, 512, 1000]

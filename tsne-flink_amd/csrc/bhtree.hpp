@@ -119,7 +119,7 @@ struct BHTree {
     int rt_skip = 0;            // builds left before the root-tile test is tried again
     double near_dmax = 0.0;     // this build's near-exact radius (squared distance), bh_near_dmax
     int32_t *meta = nullptr;    // [0] = m (in-root points), [1] = root ref, [2] = moment nodes
-    // subtree moments (see bhtree.hip "Subtree moments"): per internal node
+    // subtree moments (see bhtree_impl.hpp "Subtree moments"): per internal node
     // MOM_K scaled moments about its bounding-box centre, for nodes of
     // >= MOM_MIN_POINTS points; built in chunks of MOM_CHUNK points.
     double *mom = nullptr;       // n x MOM_K

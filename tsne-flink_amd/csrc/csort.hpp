@@ -42,7 +42,7 @@ __device__ __forceinline__ bool quant_digits(double p, double W, uint32_t &q) {
 }
 
 // The 2-D tree's key of point (px, py) in the root cell (0, 0, W): one device
-// function for morton_keys (bhtree.hip) and the fused sort front end
+// function for morton_keys (bhtree_build.hip) and the fused sort front end
 // (csort_run_fused2), so both chains sort the same keys.
 __device__ __forceinline__ uint64_t morton2_key(double px, double py, double W) {
     double x = 0.0, y = 0.0, hw = W, hh = W;
@@ -103,7 +103,7 @@ struct CoherentSort {
 
 // What the 2-D tree build takes from the sorted order, written by the fused
 // chain's bucket workgroups instead of by count_in_root, gather_sorted and
-// dup_count (bhtree.hip; the same values).
+// dup_count (bhtree_build.hip; the same values).
 struct Csort2Out {
     double2 *pos;       // pos[s] = Y[idx_sorted[s]]
     int32_t *inv;       // inv[idx_sorted[s]] = s

@@ -2,7 +2,7 @@
 // gfx950 (the SURVEY.md 8f extension of QuadTree.scala:38-152 /
 // Cell.scala:31-36 to nComponents = 3; restated in oracle/tsne_oracle.c).
 //
-// Same equivalence argument as bhtree.hip: Morton digits replay the cell
+// Same equivalence argument as bhtree_build.hip: Morton digits replay the cell
 // arithmetic (child centres c -/+ 0.5 h, closed containment tried in the
 // order upper NW, NE, SW, SE, lower NW, NE, SW, SE), so cells are the
 // restatement's; a cell whose points all sit in one child forms a chain
@@ -96,7 +96,7 @@ __global__ void morton3_keys(const double *__restrict__ Y, int64_t n, const doub
 }
 
 // m = index of the first OUT_KEY3 in the sorted keys (64-ary search by one
-// wave; see bhtree.hip count_in_root)
+// wave; see bhtree_build.hip count_in_root)
 __global__ void count_in_root3(const uint64_t *__restrict__ ks, int64_t n, int32_t *__restrict__ meta) {
     const int lane = lane_id();
     int64_t lo = 0, hi = n;
@@ -194,7 +194,7 @@ __device__ __forceinline__ double ld_sys3(const double *p) {
     return __hip_atomic_load(const_cast<double *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// Bottom-up sums / boxes / hmin / rball (bhtree.hip bottom_up, one more axis;
+// Bottom-up sums / boxes / hmin / rball (bhtree_build.hip bottom_up, one more axis;
 // the same LDS hand-off for nodes inside the workgroup's BLK leaves).
 template <int BLK>
 __global__ __launch_bounds__(BLK) void bottom_up3(const double4 *__restrict__ pos, const int32_t *__restrict__ meta,
@@ -345,7 +345,7 @@ __device__ __forceinline__ bool summarise3(double h, double dx, double dy, doubl
     return h / D < theta;
 }
 
-// ---- Subtree moments in 3-D (the 2-D moment path of bhtree.hip, restated
+// ---- Subtree moments in 3-D (the 2-D moment path of bhtree_impl.hpp, restated
 // for the octree).  For a node with box centre c and a query q: v = q - c,
 // A = |v|^2, B = 1 / (1 + A), and per point P = p - c, s = |P|^2,
 // delta = D - A = s - 2 v.P.  Then
@@ -1444,7 +1444,7 @@ void oct_build(tsne_ctx *ctx, OctTree &t, const double *dY, double theta, bool l
 }
 
 // Largest D with 72 theta^2 D^2 (1 + 8 D) <= the near-exact tolerance
-// (Options::near_tol3_early / near_tol3_late): the 2-D bound (bhtree.hip
+// (Options::near_tol3_early / near_tol3_late): the 2-D bound (bhtree_build.hip
 // bh_near_dmax) scaled by 12/8 for the larger 3-D cell diagonal (second-order
 // remainder (2 + 8D) r^2 / 2 with r^2 <= 12 h^2 instead of 8 h^2).
 static double oct_near_dmax(const tsne_ctx *ctx, double theta, bool late) {

@@ -52,7 +52,7 @@ static_assert(sizeof(ORec) % 16 == 0, "records are fetched in 16-byte pieces");
 constexpr int LEVELS3 = 21;                 // 63 key bits
 constexpr uint64_t OUT_KEY3 = 1ull << 63;   // outside the root cell: sorts last
 
-// fixed-point digits away from cell boundaries (see bhtree.hip quant_digits):
+// fixed-point digits away from cell boundaries (see csort.hpp quant_digits):
 // 21 levels, band 1e-4 of a level-21 cell
 __device__ __forceinline__ bool quant21(double p, double W, uint32_t &q) {
     const double t = (p + W) / (2.0 * W) * 2097152.0;   // 2^21
@@ -93,7 +93,7 @@ __device__ __forceinline__ uint64_t morton3_key(double px, double py, double pz,
         const bool inS = (__dsub_rn(ys, nh) <= py) && (__dadd_rn(ys, nh) >= py);
         const bool inU = (__dsub_rn(zu, nh) <= pz) && (__dadd_rn(zu, nh) >= pz);
         const bool inL = (__dsub_rn(zl, nh) <= pz) && (__dadd_rn(zl, nh) >= pz);
-        int c = 7;   // lower SE, or a rounding gap (see bhtree.hip)
+        int c = 7;   // lower SE, or a rounding gap (see csort.hpp morton2_key)
         for (int t = 0; t < 8; ++t) {
             const bool ok = ((t & 1) ? inE : inW) && ((t & 2) ? inS : inN) && ((t & 4) ? inL : inU);
             if (ok) { c = t; break; }

@@ -5,7 +5,7 @@
 //   ex  = earlyExaggeration if t <= min(T,20) + min(T-20, 81) else 1
 //   mom = initialMomentum if t <= min(T,20) else finalMomentum
 //   1. quadtree of the full Y (every rank builds the identical tree), or the
-//      root-tile shortcut while the embedding is small (bhtree.hip)
+//      root-tile shortcut while the embedding is small (bhtree_build.hip)
 //   2. BH repulsion for this rank's own points (its query list)
 //   3. Z = sum z (TsneHelpers.scala:266): the per-iteration all-reduce
 //   4. attraction per owned row of P over the CSR row (q = 1/(1+metric(y_i,

@@ -1,7 +1,7 @@
 // transform.hip -- embedding new points into a fitted map on gfx950.
 //
 // The reference map Yr (n x C, C = 2 or 3) is fixed: its tree is built once --
-// the quadtree with the records of bh_build (bhtree.hip) for C = 2, the octree
+// the quadtree with the records of bh_build (bhtree_build.hip) for C = 2, the octree
 // with the octal records of build_orec (octree.hip) for C = 3 -- and new
 // points are QUERIES that are not in the tree.  The records already mean the
 // right thing for such a query: a leaf contributes 0 when its point equals
@@ -377,7 +377,7 @@ __device__ __forceinline__ void foreign_walk3(X3LDS &L, int w, int lane, const X
 }
 
 // ---- Exact duplicates in the octree: the restatement's multiplicities (the
-// 2-D rule of bhtree.hip "Exact duplicates", restated for the transform's
+// 2-D rule of bhtree_build.hip "Exact duplicates", restated for the transform's
 // octree; the fit's tree keeps full multiplicity).  The
 // restatement keeps one leaf per distinct point and counts every copy on the
 // way down, but when a leaf holding copies of v splits (a different point
