@@ -307,7 +307,14 @@ int tsne_ctx_loop_profile(tsne_ctx *ctx, char *buf, int64_t cap, int64_t *len_ou
  *                        summed (option "tile_stream"), over every traversal;
  *   "xform3.pops"        with option "transform_stats": stack pops (wave level,
  *                        64 queries per wave) of the last 3-D
- *                        tsne_[dev_]repulsion_queries_c walk. */
+ *                        tsne_[dev_]repulsion_queries_c walk;
+ *   "knn.fallback_queries"  queries of the handle's last tsne_[dev_]knn /
+ *                        tsne_[dev_]knn_cross call that the exact fp64 scan
+ *                        answered instead of the filter + re-rank (candidate
+ *                        buffer overflow, a crowd at the k-th distance, or k
+ *                        beyond the cross form's buffers), summed over the cross
+ *                        form's query slices and a group's ranks.  Kept on the
+ *                        host: no synchronisation; no result depends on it. */
 int tsne_ctx_counter(tsne_ctx *ctx, const char *name, int64_t *value_out);
 
 /* Diagnostics (option "wave_log" with "rep_stats"): the last counting

@@ -230,15 +230,56 @@ __device__ __forceinline__ int64_t find_in_row(const int32_t *__restrict__ scol,
     return b;
 }
 
+// A row that names a column more than once (the reference sums such entries,
+// groupBy(0, 1).reduce): merged[i] = the row's distinct columns.
+__global__ void merged_rowlen(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ scol, int64_t n,
+                              int64_t *__restrict__ merged) {
+    const int64_t i = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int64_t rb = row_ptr[i], re = row_ptr[i + 1];
+    long long c = 0;
+    for (int64_t t = rb + lane_id(); t < re; t += 64) c += (t == rb || scol[t] != scol[t - 1]);
+    c = wave_sum(c);
+    if (lane_id() == 0) merged[i] = c;
+    if (i == 0 && lane_id() == 0) merged[n] = 0;
+}
+
+// One entry per distinct column at the position of its first copy, the
+// copies' values summed in their (stable-sorted = input) order.
+__global__ void merge_repeats(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ scol,
+                              const double *__restrict__ sval, int64_t n, const int64_t *__restrict__ mptr,
+                              int32_t *__restrict__ mcol, double *__restrict__ mval) {
+    const int64_t i = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int64_t rb = row_ptr[i], re = row_ptr[i + 1];
+    int64_t o = mptr[i];
+    for (int64_t t0 = rb; t0 < re; t0 += 64) {
+        const int64_t t = t0 + lane_id();
+        const bool head = t < re && (t == rb || scol[t] != scol[t - 1]);
+        const uint64_t hm = __ballot(head);
+        if (head) {
+            const int32_t j = scol[t];
+            double v = sval[t];
+            for (int64_t u = t + 1; u < re && scol[u] == j; ++u) v += sval[u];
+            const int64_t pos = o + __popcll(hm & lanemask_lt());
+            mcol[pos] = j;
+            mval[pos] = v;
+        }
+        o += __popcll(hm);
+    }
+}
+
 // pass 1: per entry (i, j): mutual?  count reverse entries per target row.
+// repeat[0] = 1 if a (sorted) row holds two equal neighbours.
 __global__ void sym_count(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ scol,
                           int64_t n, int32_t *__restrict__ mutual_pos,
-                          int32_t *__restrict__ rev_cnt) {
+                          int32_t *__restrict__ rev_cnt, int32_t *__restrict__ repeat) {
     const int64_t i = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
     if (i >= n) return;
     const int lane = lane_id();
     for (int64_t t = row_ptr[i] + lane; t < row_ptr[i + 1]; t += 64) {
         int32_t j = scol[t];
+        if (t > row_ptr[i] && scol[t - 1] == j) repeat[0] = 1;
         int64_t jb = row_ptr[j], je = row_ptr[j + 1];
         int64_t pos = find_in_row(scol, jb, je, (int32_t)i);
         bool mutual = pos < je && scol[pos] == (int32_t)i;
@@ -387,16 +428,17 @@ int64_t joint_device(tsne_ctx *ctx, const int64_t *d_row_ptr, const int32_t *d_c
     Workspace &ws = ctx->ws;
     std::vector<int64_t> hrp(n + 1);
     TSNE_HIP(hipMemcpyAsync(hrp.data(), d_row_ptr, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, st));
-    int32_t *flag = ws.get<int32_t>("sym.flag", 1);
-    TSNE_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
+    int32_t *flag = ws.get<int32_t>("sym.flag", 2);   // [0] a row unsorted, [1] a sorted row repeats a column
+    TSNE_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int32_t), st));
     hipLaunchKernelGGL(rows_unsorted, dim3(ceil_div(n, 4)), dim3(256), 0, st, d_row_ptr, d_col, n, flag);
     int32_t unsorted = 0;
     TSNE_HIP(hipMemcpyAsync(&unsorted, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TSNE_HIP(hipStreamSynchronize(st));
-    const int64_t nnz = hrp[n];
+    int64_t nnz = hrp[n];
     TSNE_REQUIRE(hrp[0] == 0, "row_ptr[0] must be 0");
     // 1. every input row sorted by column (stable, so duplicate columns keep
     // order); rows that already are (a full distance matrix) are used in place
+    const int64_t *rp = d_row_ptr;
     const int32_t *scol = d_col;
     const double *sval = d_p;
     if (unsorted) {
@@ -406,22 +448,45 @@ int64_t joint_device(tsne_ctx *ctx, const int64_t *d_row_ptr, const int32_t *d_c
         scol = c2;
         sval = v2;
     }
-    // 2. mutual lookup + reverse counts
+    // 2. mutual lookup + reverse counts; the same pass (the first over sorted
+    // rows) sees whether a row repeats a column
     int32_t *mpos = ws.get<int32_t>("sym.mpos", nnz + 1);
     int32_t *rev = ws.get<int32_t>("sym.rev", n);
-    TSNE_HIP(hipMemsetAsync(rev, 0, n * sizeof(int32_t), st));
-    hipLaunchKernelGGL(sym_count, dim3(ceil_div(n, 4)), dim3(256), 0, st, d_row_ptr, scol, n, mpos, rev);
     int64_t *len = ws.get<int64_t>("sym.len", n + 1);
-    hipLaunchKernelGGL(sym_rowlen, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_row_ptr, rev, n, len);
     int64_t *excl = ws.get<int64_t>("sym.excl", n + 1);
     size_t tb2 = 0;
     TSNE_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, len, excl, (int)n + 1, st));
     void *tmp2 = ws.get<uint8_t>("sym.tmp2", tb2);
-    TSNE_HIP(hipMemsetAsync(len + n, 0, sizeof(int64_t), st));
-    TSNE_HIP(hipcub::DeviceScan::ExclusiveSum(tmp2, tb2, len, excl, (int)n + 1, st));
     int64_t total = 0;
-    TSNE_HIP(hipMemcpyAsync(&total, excl + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    TSNE_HIP(hipStreamSynchronize(st));
+    int32_t repeats = 0;
+    auto count = [&]() {
+        TSNE_HIP(hipMemsetAsync(rev, 0, n * sizeof(int32_t), st));
+        hipLaunchKernelGGL(sym_count, dim3(ceil_div(n, 4)), dim3(256), 0, st, rp, scol, n, mpos, rev, flag + 1);
+        hipLaunchKernelGGL(sym_rowlen, dim3(ceil_div(n, 256)), dim3(256), 0, st, rp, rev, n, len);
+        TSNE_HIP(hipMemsetAsync(len + n, 0, sizeof(int64_t), st));
+        TSNE_HIP(hipcub::DeviceScan::ExclusiveSum(tmp2, tb2, len, excl, (int)n + 1, st));
+        TSNE_HIP(hipMemcpyAsync(&total, excl + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        TSNE_HIP(hipMemcpyAsync(&repeats, flag + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TSNE_HIP(hipStreamSynchronize(st));
+    };
+    count();
+    if (repeats) {
+        // the reference sums the entries of one (row, column): merge each run
+        // of equal columns into its first entry, then look up again
+        int64_t *mptr = ws.get<int64_t>("sym.mptr", n + 1);
+        hipLaunchKernelGGL(merged_rowlen, dim3(ceil_div(n, 4)), dim3(256), 0, st, rp, scol, n, len);
+        TSNE_HIP(hipcub::DeviceScan::ExclusiveSum(tmp2, tb2, len, mptr, (int)n + 1, st));
+        int32_t *c3 = ws.get<int32_t>("sym.mcol", nnz + 1);
+        double *v3 = ws.get<double>("sym.mval", nnz + 1);
+        hipLaunchKernelGGL(merge_repeats, dim3(ceil_div(n, 4)), dim3(256), 0, st, rp, scol, sval, n, mptr, c3, v3);
+        TSNE_LAUNCH_CHECK();
+        TSNE_HIP(hipMemcpyAsync(&nnz, mptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        TSNE_HIP(hipMemsetAsync(flag + 1, 0, sizeof(int32_t), st));
+        rp = mptr;
+        scol = c3;
+        sval = v3;
+        count();
+    }
     if (total > cap) { ws.release_prefix("sym."); return total; }
     // 3. fill (own entries in place, reverse entries appended), then sort each
     // output row by column -- not needed when no row received a reverse entry
@@ -430,7 +495,7 @@ int64_t joint_device(tsne_ctx *ctx, const int64_t *d_row_ptr, const int32_t *d_c
     int32_t *ucol = any_rev ? ws.get<int32_t>("sym.ucol", total + 1) : d_out_col;
     double *uval = any_rev ? ws.get<double>("sym.uval", total + 1) : d_out_val;
     TSNE_HIP(hipMemsetAsync(rev, 0, n * sizeof(int32_t), st));
-    hipLaunchKernelGGL(sym_fill, dim3(ceil_div(n, 4)), dim3(256), 0, st, d_row_ptr, scol, sval, mpos,
+    hipLaunchKernelGGL(sym_fill, dim3(ceil_div(n, 4)), dim3(256), 0, st, rp, scol, sval, mpos,
                        n, excl, rev, ucol, uval);
     TSNE_LAUNCH_CHECK();
     hipLaunchKernelGGL(copy_row_ptr, dim3(ceil_div(n + 1, 256)), dim3(256), 0, st, excl, n, total,

@@ -44,6 +44,11 @@ static void check_ctx(tsne_ctx *ctx) {
 
 // Single-device operators on a group handle run on its first rank.
 static tsne_ctx *primary(tsne_ctx *ctx) { return ctx->group.empty() ? ctx : ctx->group[0]; }
+// a kNN call starts: "knn.fallback_queries" is summed over the ranks, and a
+// rank the call gives no queries must not keep an earlier call's count
+static void knn_counter_reset(tsne_ctx *ctx) {
+    for (tsne_ctx *c : ctx->group) c->knn_fallback_queries = 0;
+}
 
 // The device-resident optimizer (tsne_dev_opt_*) is one rank's state: on a
 // tsne_ctx_create_multi handle of several ranks its first context is rank 0 of
@@ -434,9 +439,15 @@ int tsne_ctx_counter(tsne_ctx *ctx, const char *name, int64_t *value_out) {
     return guard([&] {
         check_ctx(ctx);
         TSNE_REQUIRE(name != nullptr && value_out != nullptr, "NULL argument");
+        const std::string k = name;
+        if (k == "knn.fallback_queries") {   // host-side count: no stream to wait for, summed over a group's ranks
+            int64_t s = ctx->knn_fallback_queries;
+            for (const tsne_ctx *c : ctx->group) s += c->knn_fallback_queries;
+            *value_out = s;
+            return;
+        }
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
-        const std::string k = name;
         if (k == "bh.narrow_groups") *value_out = ctx->single_tree ? bh_narrow_groups(ctx, *ctx->single_tree) : 0;
         else if (k == "opt.narrow_groups") *value_out = opt_tree(ctx) ? bh_narrow_groups(ctx, *opt_tree(ctx)) : 0;
         else if (k == "opt.wave_mhz") *value_out = opt_wave_mhz(ctx);
@@ -547,6 +558,7 @@ int tsne_dev_knn(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t 
                  int64_t q0, int64_t q1, int32_t *d_idx, double *d_dist) {
     return guard([&] {
         check_ctx(ctx);
+        knn_counter_reset(ctx);
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
         knn_device(ctx, dX, n, d, metric, k, q0, q1, d_idx, d_dist);
@@ -660,6 +672,7 @@ int tsne_knn(tsne_ctx *ctx, const double *X, int64_t n, int32_t d, int32_t metri
              int64_t q0, int64_t q1, int32_t *idx_out, double *dist_out) {
     return guard([&] {
         check_ctx(ctx);
+        knn_counter_reset(ctx);
         TSNE_REQUIRE(X && idx_out && dist_out, "NULL buffer");
         TSNE_REQUIRE(n >= 2 && d >= 1 && k >= 1, "bad sizes");
         TSNE_REQUIRE(q0 >= 0 && q1 <= n && q0 <= q1, "query range out of bounds");
@@ -978,6 +991,7 @@ int tsne_knn_cross(tsne_ctx *ctx, const double *X, int64_t n, const double *Xq, 
                    int32_t metric, int32_t k, int32_t *idx_out, double *dist_out) {
     return guard([&] {
         check_ctx(ctx);
+        knn_counter_reset(ctx);
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
         TSNE_REQUIRE(n >= 1 && m >= 0 && d >= 1 && k >= 1, "bad sizes");
@@ -999,6 +1013,7 @@ int tsne_dev_knn_cross(tsne_ctx *ctx, const double *dX, int64_t n, const double 
                        int32_t metric, int32_t k, int32_t *d_idx, double *d_dist) {
     return guard([&] {
         check_ctx(ctx);
+        knn_counter_reset(ctx);
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
         knn_cross_device(ctx, dX, n, dXq, m, d, metric, k, d_idx, d_dist);

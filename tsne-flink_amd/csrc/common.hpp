@@ -263,6 +263,7 @@ struct tsne_ctx {
     tsne::StageTimers timers;
     int32_t *pinned = nullptr;   // small pinned host scratch (per-iteration read-backs)
     int cu_count = 256;
+    int64_t knn_fallback_queries = 0;   // queries of the last kNN call answered by the exact scan ("knn.fallback_queries")
     // tsne_ctx_create_multi: the per-device contexts (ranks) of a group
     // handle; host-buffer operators fan out over them, one thread per rank
     std::vector<tsne_ctx *> group;

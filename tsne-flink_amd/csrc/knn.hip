@@ -21,7 +21,9 @@
 //              contraction) and bitonic-sorts them by (d, j) in LDS.
 //   5. fallback: a query whose buffer overflows (only pathological crowds of
 //              near-equal distances, e.g. many duplicate points) is redone by
-//              an exact fp64 scan + stable radix sort.
+//              an exact fp64 scan + stable radix sort.  So is every query of
+//              an input whose fp32 squares overflow (no finite d32 to filter
+//              by).  tsne_ctx_counter "knn.fallback_queries" counts them.
 #include <algorithm>
 
 #include <hipcub/hipcub.hpp>
@@ -751,7 +753,11 @@ void knn_run(tsne_ctx *ctx, const double *dX, int64_t n, int64_t nc, int32_t d, 
     int32_t *cand_j = ws.get<int32_t>("knn.cand_j", (size_t)nq * CAP);
     TSNE_HIP(hipMemsetAsync(flags, 0, nq * sizeof(int32_t), st));
     std::vector<int32_t> hflags(nq);
-    if (scan_only) {
+    // The filters need finite d32: |d32| <= |q|^2 + |c|^2 + 2 |q.c| <= 4 nmax.
+    // Beyond that (fp32 squares that overflow: |x - mean| ~ 1e19) a near
+    // pair's inf - inf = NaN fails every d32 <= tau and is dropped while far
+    // pairs stay, so the filter is not a superset any more: exact scan.
+    if (scan_only || !(nmax <= 0x1p125f)) {
         std::fill(hflags.begin(), hflags.end(), 1);
     } else {
     const int64_t qtiles = ceil_div(nq, TQ);
@@ -800,9 +806,10 @@ void knn_run(tsne_ctx *ctx, const double *dX, int64_t n, int64_t nc, int32_t d, 
     TSNE_HIP(hipMemcpyAsync(hflags.data(), flags, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TSNE_HIP(hipStreamSynchronize(st));
     }
-    bool any = false;
-    for (int64_t i = 0; i < nq && !any; ++i) any = hflags[i] != 0;
-    if (!any) return;
+    int64_t nfb = 0;   // tsne_ctx_counter "knn.fallback_queries"
+    for (int64_t i = 0; i < nq; ++i) nfb += hflags[i] != 0;
+    ctx->knn_fallback_queries += nfb;
+    if (nfb == 0) return;
     uint64_t *keys = ws.get<uint64_t>("knn.fb_keys", nc);
     uint64_t *keys2 = ws.get<uint64_t>("knn.fb_keys2", nc);
     int32_t *vals = ws.get<int32_t>("knn.fb_vals", nc);
@@ -826,6 +833,7 @@ void knn_run(tsne_ctx *ctx, const double *dX, int64_t n, int64_t nc, int32_t d, 
 
 void knn_device(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t metric, int32_t k,
                 int64_t q0, int64_t q1, int32_t *d_idx, double *d_dist) {
+    ctx->knn_fallback_queries = 0;
     TSNE_REQUIRE(n >= 2, "kNN needs at least two points");
     TSNE_REQUIRE(d >= 1, "dimension must be positive");
     TSNE_REQUIRE(k >= 1, "k must be positive");
@@ -850,6 +858,7 @@ void knn_device(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t m
 // takes the exact scan for every query.
 void knn_cross_device(tsne_ctx *ctx, const double *dX, int64_t n, const double *dXq, int64_t m, int32_t d,
                       int32_t metric, int32_t k, int32_t *d_idx, double *d_dist) {
+    ctx->knn_fallback_queries = 0;   // summed over the query slices below
     TSNE_REQUIRE(n >= 1 && m >= 0, "cross kNN needs at least one reference row");
     TSNE_REQUIRE(d >= 1, "dimension must be positive");
     TSNE_REQUIRE(k >= 1, "k must be positive");
