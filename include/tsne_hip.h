@@ -146,6 +146,13 @@ int tsne_ctx_synchronize(tsne_ctx *ctx);
  *   "attract_dyn" 1           attract_tiles: the waves claim a tile's slices
  *                             instead of taking every 16th (non-loss launches;
  *                             identical results);
+ *   "attract_stream" 1        2-D tiled attraction with "attract_pipe" 0: the
+ *                             non-loss launches read a second storage of the
+ *                             tiles (each wave's entries of a row block one
+ *                             contiguous stream, every step padded to 64
+ *                             lanes with zero values) through a ring of
+ *                             unconditional wide loads (attract_tiles_stream;
+ *                             identical results; 0: attract_tiles only);
  *   "graph_order" 1           P's graph order as the initial labels;
  *   "relabel" -1              Morton relabels: -1 automatic, 0 never, 1 by
  *                             locality score, 2 always;
@@ -295,6 +302,8 @@ int tsne_ctx_loop_profile(tsne_ctx *ctx, char *buf, int64_t cap, int64_t *len_ou
  *   "opt.attract_kernel" the optimizer's attraction kernel: 0 attract_rows,
  *                        1 attract_tiles, 2 attract3 (3-D), 3 attract_tiles3
  *                        (3-D, tiled), -1 no optimizer;
+ *   "opt.attract_pad_ppm" the stream layout's stored slots per real entry,
+ *                        in parts per million (>= 1000000; 0: not built);
  *   "opt.csort_oversized_total"  the same summed over every build of the optimizer's tree;
  *   "bh.csort_oversized", "opt.csort_oversized"  buckets of the last coherent
  *                        Morton sort (csort.hpp) beyond its LDS capacity;

@@ -132,6 +132,7 @@ static const OptionField k_options[] = {
     {"attract_cfg", nullptr, &Options::attract_cfg, -1, 3},
     {"attract_pipe", nullptr, &Options::attract_pipe, 0, 5},
     {"attract_dyn", nullptr, &Options::attract_dyn, 0, 1},
+    {"attract_stream", nullptr, &Options::attract_stream, 0, 1},
     {"graph_order", nullptr, &Options::graph_order, 0, 1},
     {"relabel", nullptr, &Options::relabel, -1, 2},
     {"recut", nullptr, &Options::recut, 0, 1},
@@ -453,6 +454,7 @@ int tsne_ctx_counter(tsne_ctx *ctx, const char *name, int64_t *value_out) {
         else if (k == "opt.wave_mhz") *value_out = opt_wave_mhz(ctx);
         else if (k == "bh.csort_oversized") *value_out = ctx->single_tree ? csort_oversized(ctx, ctx->single_tree->cs) : 0;
         else if (k == "opt.attract_kernel") *value_out = opt_attract_kernel(ctx);
+        else if (k == "opt.attract_pad_ppm") *value_out = opt_attract_pad(ctx);
         else if (k == "bh.spill_tasks" || k == "bh.spill_flags")
             *value_out = ctx->single_tree ? bh_spill_counter(ctx, *ctx->single_tree, k == "bh.spill_flags") : 0;
         else if (k == "opt.spill_tasks" || k == "opt.spill_flags")

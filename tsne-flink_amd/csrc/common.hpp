@@ -188,6 +188,9 @@ struct Options {
     int attract_cfg = -1;     // its tile shape: -1 by rows per rank, else ATCfg0..3
     int attract_pipe = 0;     // 2-D tiled attraction: 0 attract_tiles, 1..5 attract_tiles_pipe shapes (round 6)
     int attract_dyn = 1;      // attract_tiles: a tile's slices claimed by the waves (round 6; same sums)
+    int attract_stream = 1;   // 2-D tiled attraction, non-loss launches, attract_pipe 0: the stream layout (every
+                              // wave's entries of a row block contiguous and padded to 64 lanes a step) and
+                              // attract_tiles_stream (round 10; same sums)
     int graph_order = 1;      // P's graph order (components + BFS) as the initial labels
     int relabel = -1;         // -1 automatic, 0 never, 1 by the locality score, 2 always
     int recut = 0;            // several ranks on the tiled layout: re-cut by BH cost instead of relabels
@@ -332,6 +335,7 @@ void opt_profile(tsne_ctx *ctx, int enable, double *ms5, int64_t *visits);
 double opt_last_z(tsne_ctx *ctx);
 int32_t opt_attract_log(tsne_ctx *ctx, int32_t *iters, int32_t *standalone, double *ms, int32_t cap);
 void opt_destroy(tsne_ctx *ctx);
+int64_t opt_attract_pad(tsne_ctx *ctx);      // stream layout: stored slots per real entry, in parts per million (0: not built)
 int64_t opt_attract_kernel(tsne_ctx *ctx);   // the optimizer's attraction: 0 attract_rows, 1 attract_tiles, 2 attract3,
                                               // 3 attract_tiles3 (-1: none)
 BHTree *opt_tree(tsne_ctx *ctx);   // the optimizer's 2-D tree (nullptr without one)

@@ -46,6 +46,13 @@ struct ASlice {
     int32_t cnt;     // segments (rows): <= 64, or 1 for a wide slice
 };
 
+struct AWave {       // stream layout (attract_tiles_stream): a wave's share of a row block
+    int32_t q0;      // its first slice in the dealt list
+    int32_t cnt;     // its slices
+    int32_t steps;   // the sum of their widths
+    int32_t g0;      // its stream's first group
+};
+
 struct OptState {
     tsne_params p{};
     int C = 2;
@@ -128,6 +135,13 @@ struct OptState {
     uint32_t *at_srow = nullptr;
     uint16_t *at_pk = nullptr;
     double *at_pv = nullptr;
+    // the stream layout of the same slices (attract_tiles_stream; Options::attract_stream)
+    bool at_stream = false;
+    int64_t at_pad_ppm = 0;   // its stored slots (64 per step) per real entry, in parts per million
+    AWave *ats_waves = nullptr;
+    int2 *ats_recs = nullptr;
+    uint32_t *ats_lword = nullptr;
+    uint8_t *ats_stream = nullptr;
     double last_ms[5] = {0, 0, 0, 0, 0};
     int64_t last_visits[10] = {};
     int64_t last_mhz = 0;   // the traced traversal's waves' shader clock (MHz)
@@ -847,6 +861,238 @@ __global__ __launch_bounds__(CF::NT) void attract_tiles_pipe(
     }
 }
 
+// ---- attract_tiles over the stream layout (Options::attract_stream, round 10)
+// attract_tiles moves 290 B per vector-memory instruction (2-byte and 8-byte
+// loads, exec-masked by the lane's row length, each step's base a ballot
+// chain) and has nothing in flight while it sums a slice.  The stream layout
+// stores the same tiles, slices, lanes and per-row entry order a second time,
+// arranged for the fetch: a tile's slices are dealt to the 16 waves when the
+// layout is built (by total width), and all the steps a wave runs in a row
+// block -- slice after slice, tile after tile -- form one contiguous stream.
+// Every step holds all 64 lanes: a lane past its row's end gets the value +0.0
+// and the column of the lane's first entry in the slice (no row: column 0), so
+// its term adds +-0 to a sum that is never -0, from a point the row has read
+// already.  The steps go in groups of four (ATS_GBYTES per group: lane l's
+// values of steps 0-1 at 16 l, of steps 2-3 at 1024 + 16 l, its four 16-bit
+// columns at 2048 + 8 l); groups run across slices and tiles, so only the end
+// of a wave's stream is padded to a group.  A wave reads its stream through a
+// ring of ATS_D groups of registers: three unconditional buffer loads per
+// group, the descriptor covering the wave's own stream and the offset advanced
+// by a constant, on every path, so the compiler counts the loads in flight and
+// the ring keeps issuing through slice switches and tile barriers.  A slice
+// switch takes the lane word (from the dealt list, two slices ahead) and y_i
+// (one slice ahead; see ats_wait_but), and adds the finished slice's sums to
+// the rows' accumulators as attract_tiles does.  Each (row, tile) sum and each accumulator receives
+// the same operations in the same order as in attract_tiles: bit-identical.
+constexpr int ATS_GBYTES = 64 * (4 * 8 + 4 * 2);   // a group: four steps of 64 lanes
+constexpr int ATS_D = 4;                           // groups in flight per wave (10 KB; 40 VGPRs)
+typedef uint32_t ats_u4 __attribute__((ext_vector_type(4)));
+typedef uint32_t ats_u2 __attribute__((ext_vector_type(2)));
+struct ATSGroup {
+    ats_u4 a, b;   // values: steps 0-1, 2-3
+    ats_u2 c;      // columns: four steps
+};
+#ifndef ATS_DEFECT
+#define ATS_DEFECT 0   // 1, 3, 4: seeded defects for tests/test_gpu_attract_stream.py (never in a product build)
+#endif
+// a group's three loads; `goff` (the group's byte offset) goes into the range-checked
+// vector offset, so that a group past the wave's stream reads zeros and moves nothing
+__device__ __forceinline__ void ats_issue(ATSGroup &r, __amdgpu_buffer_rsrc_t rs, int lane, uint32_t goff) {
+    // read once per launch: nontemporal (aux bit 1)
+    r.a = __builtin_amdgcn_raw_buffer_load_b128(rs, goff + (uint32_t)lane * 16u, 0, 2);
+    r.b = __builtin_amdgcn_raw_buffer_load_b128(rs, goff + (uint32_t)lane * 16u + 1024u, 0, 2);
+    r.c = __builtin_amdgcn_raw_buffer_load_b64(rs, goff + (uint32_t)lane * 8u + 2048u, 0, 2);
+}
+template <int U>
+__device__ __forceinline__ double ats_val(const ATSGroup &r) {
+    return U == 0 ? __hiloint2double((int)r.a.y, (int)r.a.x) : U == 1 ? __hiloint2double((int)r.a.w, (int)r.a.z)
+         : U == 2 ? __hiloint2double((int)r.b.y, (int)r.b.x) : __hiloint2double((int)r.b.w, (int)r.b.z);
+}
+template <int U>
+__device__ __forceinline__ uint32_t ats_col(const ATSGroup &r) {
+    return U == 0 ? (r.c.x & 0xffffu) : U == 1 ? (r.c.x >> 16) : U == 2 ? (r.c.y & 0xffffu) : (r.c.y >> 16);
+}
+
+// The slice pipeline's own loads (a lane word two slices ahead, y_i one slice
+// ahead) are consumed at the next slice switch, and the compiler, which must
+// assume the shortest path between two switches (no group issued), would wait
+// there for every load in flight: the whole ring, once per slice (measured:
+// 0.61 ms per launch against 0.67 for attract_tiles).  So these loads go
+// through registers the compiler does not manage (accumulation registers a0 ..
+// a5, written by the loads, read after the wait) and the wave counts the ring
+// loads it has issued since: loads return in order, so leaving that many in
+// flight is enough.  The compiler's own counts are unaware of these loads and
+// therefore wait for at most two loads more than they need.
+template <int P>
+__device__ __forceinline__ void ats_lword_load(const uint32_t *p) {
+    if (P == 0) asm volatile("global_load_dword a0, %0, off" : : "v"(p) : "a0", "memory");
+    else asm volatile("global_load_dword a1, %0, off" : : "v"(p) : "a1", "memory");
+}
+template <int P>
+__device__ __forceinline__ uint32_t ats_lword_read() {
+    uint32_t v;
+    if (P == 0) asm volatile("v_accvgpr_read_b32 %0, a0" : "=v"(v) : : "memory");
+    else asm volatile("v_accvgpr_read_b32 %0, a1" : "=v"(v) : : "memory");
+    return v;
+}
+__device__ __forceinline__ void ats_yi_load(const double2 *p) {
+    asm volatile("global_load_dwordx4 a[2:5], %0, off" : : "v"(p) : "a2", "a3", "a4", "a5", "memory");
+}
+__device__ __forceinline__ double2 ats_yi_read() {
+    uint32_t x0, x1, y0, y1;
+    asm volatile("v_accvgpr_read_b32 %0, a2\n\tv_accvgpr_read_b32 %1, a3\n\t"
+                 "v_accvgpr_read_b32 %2, a4\n\tv_accvgpr_read_b32 %3, a5"
+                 : "=v"(x0), "=v"(x1), "=v"(y0), "=v"(y1) : : "memory");
+    return make_double2(__hiloint2double((int)x1, (int)x0), __hiloint2double((int)y1, (int)y0));
+}
+// everything but the last `c` loads (c: ring loads issued since the loads waited for)
+__device__ __forceinline__ void ats_wait_but(int c) {
+    if (c >= 9) asm volatile("s_waitcnt vmcnt(9)" : : : "memory");
+    else if (c >= 6) asm volatile("s_waitcnt vmcnt(6)" : : : "memory");
+    else if (c >= 3) asm volatile("s_waitcnt vmcnt(3)" : : : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+}
+
+template <class CF, int MET>
+__global__ __launch_bounds__(CF::NT) void attract_tiles_stream(
+    const ATile *__restrict__ tiles, const int32_t *__restrict__ rbt, const AWave *__restrict__ waves,
+    const int2 *__restrict__ recs, const uint32_t *__restrict__ lword, const uint8_t *__restrict__ stream,
+    int64_t rows, int64_t r0, int64_t n, const double *__restrict__ Y, double ex, int64_t xcd_chunk,
+    double2 *__restrict__ attr, int64_t rbs) {
+    constexpr int RB = CF::RB, W = CF::W, NT = CF::NT, WAVES = CF::WAVES, D = ATS_D;
+    __shared__ double2 win[W];
+    __shared__ double2 acc[RB];
+    const int tid = threadIdx.x, lane = lane_id();
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t rb = xcd_chunk > 0 ? xcd_block_chunked(blockIdx.x, gridDim.x, xcd_chunk) : (int64_t)blockIdx.x;
+    const int64_t b0 = rb * rbs;
+    const int nr = (int)min(rbs, rows - b0);
+    const double2 *Y2 = reinterpret_cast<const double2 *>(Y);
+    const double2 *Yrow = Y2 + r0 + b0;
+    for (int i = tid; i < nr; i += NT) acc[i] = make_double2(0.0, 0.0);
+    const int t0 = __builtin_amdgcn_readfirstlane(rbt[rb]), t1 = __builtin_amdgcn_readfirstlane(rbt[rb + 1]);
+    if (t0 < t1) {
+        const AWave *wv = waves + rb * WAVES + w;
+        const int q0 = __builtin_amdgcn_readfirstlane(wv->q0), cnt = __builtin_amdgcn_readfirstlane(wv->cnt);
+#if ATS_DEFECT == 3
+        const int steps = max(0, ((__builtin_amdgcn_readfirstlane(wv->steps) + 3) >> 2) - 1) << 2;
+#else
+        const int steps = __builtin_amdgcn_readfirstlane(wv->steps);
+#endif
+        const int64_t g0 = __builtin_amdgcn_readfirstlane(wv->g0);
+        const int ng = (steps + 3) >> 2;
+        // the descriptor covers the wave's own stream (all of P's entries can exceed 4 GB).
+        // Every group slot issues its loads, past the stream's end too (out of range: zeros,
+        // never summed): a conditional issue would leave the compiler no load count to wait by
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<uint8_t *>(stream + g0 * ATS_GBYTES), (short)0, ng * ATS_GBYTES, 0x00020000);
+        // the slice pipeline: slice i + 2's lane word and slice i + 1's y_i in flight
+        // (list slots past the wave's slices hold other waves' words or the slack:
+        // the row is clamped, the point never used)
+        const uint32_t *lw = lword + (int64_t)q0 * 64 + lane;
+        // (the lane words of even slices in a0, of odd ones in a1, y_i in a2 .. a5)
+        ats_lword_load<0>(lw);
+        ats_lword_load<1>(lw + 64);
+        ats_wait_but(0);
+        ats_yi_load(Yrow + min((int)(ats_lword_read<0>() >> AT_LENBITS), nr - 1));
+        ATSGroup R[D];
+        uint32_t soff = 0;
+        int since = 0;   // ring loads issued since the slice pipeline's last loads
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            ats_issue(R[j], rs, lane, soff);
+            soff += ATS_GBYTES;
+            since += 3;
+        }
+        int2 rec1 = make_int2(0, t1);   // the next slice: width | wide << 31, tile
+        if (cnt > 0) {
+            rec1.x = __builtin_amdgcn_readfirstlane(recs[q0].x);
+            rec1.y = __builtin_amdgcn_readfirstlane(recs[q0].y);
+        }
+        int i = 0, tcur = t0, rem = 0, wide = 0, len = 0, lrow = 0;
+        double2 yi = make_double2(0.0, 0.0);
+        double fx = 0.0, fy = 0.0, lnone = 0.0;
+        atp_tile_begin<W, NT>(win, tiles, Y2, n, t0, tid);
+        // the finished slice's sums into its rows' accumulators (as attract_tiles)
+        auto flush = [&]() {
+            if (wide) {   // one row over the 64 lanes: a fixed-order tree (lanes without entries add 0)
+                fx = wave_sum(len > 0 ? fx : 0.0);
+                fy = wave_sum(len > 0 ? fy : 0.0);
+                if (lane == 0) {
+                    const double2 o = acc[lrow];
+                    acc[lrow] = make_double2(__dadd_rn(o.x, fx), __dadd_rn(o.y, fy));
+                }
+            } else if (len > 0) {
+                const double2 o = acc[lrow];
+                acc[lrow] = make_double2(__dadd_rn(o.x, fx), __dadd_rn(o.y, fy));
+#if ATS_DEFECT == 4   // as if wave 1's slices had been dealt to a second wave as well
+                if (w == 1) acc[lrow] = make_double2(__dadd_rn(acc[lrow].x, fx), __dadd_rn(acc[lrow].y, fy));
+#endif
+            }
+        };
+        // the barriers and window copies up to tile `to` (t1: past the last tile)
+        auto advance = [&](int to) {
+            while (tcur < to) {
+                __syncthreads();
+                tcur = __builtin_amdgcn_readfirstlane(tcur + 1);
+                if (tcur == t1) break;
+                atp_tile_begin<W, NT>(win, tiles, Y2, n, tcur, tid);
+            }
+        };
+        auto next_slice = [&](auto par) {   // the parity of slice i
+            constexpr int P = decltype(par)::value;
+            flush();
+            advance(rec1.y);
+            ats_wait_but(since);
+            const uint32_t rl1 = ats_lword_read<P>(), rl2 = ats_lword_read<1 - P>();
+            rem = rec1.x & 0x7fffffff;
+            wide = (int)((uint32_t)rec1.x >> 31);
+            len = (int)(rl1 & ((1u << AT_LENBITS) - 1));
+            lrow = (int)(rl1 >> AT_LENBITS);
+            yi = ats_yi_read();
+            fx = 0.0;
+            fy = 0.0;
+            i = __builtin_amdgcn_readfirstlane(i + 1);
+            rec1 = make_int2(0, t1);
+            if (i < cnt) {
+                rec1.x = __builtin_amdgcn_readfirstlane(recs[q0 + i].x);
+                rec1.y = __builtin_amdgcn_readfirstlane(recs[q0 + i].y);
+            }
+            ats_yi_load(Yrow + min((int)(rl2 >> AT_LENBITS), nr - 1));
+            ats_lword_load<P>(lw + (int64_t)(i + 1) * 64);
+            since = 0;
+        };
+#define TSNE_ATS_STEP(J, U)                                                                               \
+    if (((g + J) << 2) + U < steps) {                                                                     \
+        if (rem == 0) {                                                                                   \
+            if (i & 1) next_slice(std::integral_constant<int, 1>{});                                      \
+            else next_slice(std::integral_constant<int, 0>{});                                            \
+        }                                                                                                 \
+        atp_term<false, MET>(win, yi, ats_col<U>(R[J]), ats_val<U>(R[J]), ex, 1.0, fx, fy, lnone);       \
+        --rem;                                                                                            \
+    }
+        for (int g = 0; g < ng; g += D) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                if (g + j < ng) {
+                    TSNE_ATS_STEP(j, 0)
+                    TSNE_ATS_STEP(j, 1)
+                    TSNE_ATS_STEP(j, 2)
+                    TSNE_ATS_STEP(j, 3)
+                }
+                ats_issue(R[j], rs, lane, soff);   // group g + j + D
+                soff += ATS_GBYTES;
+                since += 3;
+            }
+        }
+#undef TSNE_ATS_STEP
+        ats_wait_but(0);   // the pipeline's last loads, of slices past the wave's
+        flush();
+        advance(t1);
+    }
+    for (int i = tid; i < nr; i += NT) attr[b0 + i] = make_double2(acc[i].x * ex, acc[i].y * ex);
+}
+
 // ---- tile layout build (at every relabel; see build_attract_tiles)
 // 1. key (row block * ncb + window) << rowbits | local row of every owned
 //    entry (wave per row), for a stable radix sort
@@ -1007,6 +1253,107 @@ __global__ void at_ranges(const ATile *__restrict__ tiles, int32_t nt, int64_t n
     const int64_t lo = t == 0 ? 0 : (int64_t)tiles[t - 1].rb + 1;
     const int64_t hi = t < nt ? (int64_t)tiles[t].rb : nrb;
     for (int64_t r = lo; r <= hi; ++r) rbt[r] = (int32_t)t;
+}
+
+// ---- stream layout build (attract_tiles_stream), from the tiled layout
+// The (tile, wave) regions are numbered in stream order: row block, wave,
+// tile -- region (t, w) of a row block with tiles [t0, t1) is
+// WAVES t0 + w (t1 - t0) + (t - t0).
+__device__ __forceinline__ int64_t ats_region(int32_t t0, int32_t t1, int32_t t, int w, int waves) {
+    return (int64_t)waves * t0 + (int64_t)w * (t1 - t0) + (t - t0);
+}
+// 9. one thread per tile deals its slices to the waves: each slice, in the
+//    tile's order (wide slices, then descending row length), to the wave with
+//    the fewest steps so far (the first of equals).  Per slice its wave, its
+//    rank and first step within the region; per region its slices and steps.
+template <int WAVES>
+__global__ void ats_deal(const ATile *__restrict__ tiles, int32_t nt, const ASlice *__restrict__ slices,
+                         const int32_t *__restrict__ rbt, int4 *__restrict__ deal, int32_t *__restrict__ rcnt,
+                         int32_t *__restrict__ rsteps) {
+    const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nt) return;
+    const ATile tl = tiles[t];
+    const int32_t t0 = rbt[tl.rb], t1 = rbt[tl.rb + 1];
+    int32_t load[WAVES], num[WAVES];
+    for (int w = 0; w < WAVES; ++w) load[w] = num[w] = 0;
+    for (int32_t q = 0; q < tl.ns; ++q) {
+        const int32_t s = tl.s0 + q;
+        int best = 0;
+        for (int w = 1; w < WAVES; ++w)
+            if (load[w] < load[best]) best = w;
+        deal[s] = make_int4(t, best, num[best], load[best]);
+        load[best] += slices[s].width;
+        num[best] += 1;
+    }
+    for (int w = 0; w < WAVES; ++w) {
+        const int64_t r = ats_region(t0, t1, t, w, WAVES);
+        rcnt[r] = num[w];
+        rsteps[r] = load[w];
+    }
+}
+// 10. one thread per (row block, wave): its slices, steps and groups
+//     (rq / rso: exclusive prefixes of the regions' slices / steps, with the totals at the end)
+template <int WAVES>
+__global__ void ats_waves(const int32_t *__restrict__ rbt, int64_t nrb, const int32_t *__restrict__ rq,
+                          const int32_t *__restrict__ rso, AWave *__restrict__ waves, int32_t *__restrict__ wgroups) {
+    const int64_t bw = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (bw >= nrb * WAVES) return;
+    const int64_t rb = bw / WAVES;
+    const int w = (int)(bw % WAVES);
+    const int32_t t0 = rbt[rb], t1 = rbt[rb + 1];
+    const int64_t a = ats_region(t0, t1, t0, w, WAVES), b = a + (t1 - t0);
+    AWave x;
+    x.q0 = rq[a];
+    x.cnt = rq[b] - rq[a];
+    x.steps = rso[b] - rso[a];
+    x.g0 = 0;
+    waves[bw] = x;
+    wgroups[bw] = (x.steps + 3) >> 2;
+}
+__global__ void ats_wave_g0(AWave *__restrict__ waves, const int32_t *__restrict__ wg0, int64_t nw) {
+    const int64_t bw = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (bw < nw) waves[bw].g0 = wg0[bw];
+}
+// 11. one wave per slice: its list record and lane words, and its steps into
+//     the wave's stream, every step for all 64 lanes (see attract_tiles_stream)
+template <int WAVES>
+__global__ void ats_fill(const ASlice *__restrict__ slices, int32_t nsl, const ATile *__restrict__ tiles,
+                         const int32_t *__restrict__ rbt, const int4 *__restrict__ deal,
+                         const int32_t *__restrict__ rq, const int32_t *__restrict__ rso,
+                         const AWave *__restrict__ waves, const uint32_t *__restrict__ srow,
+                         const uint16_t *__restrict__ pk, const double *__restrict__ pv, int2 *__restrict__ recs,
+                         uint32_t *__restrict__ lword, uint8_t *__restrict__ stream) {
+    const int64_t s = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (s >= nsl) return;
+    const int lane = lane_id();
+    const ASlice sd = slices[s];
+    const int4 dl = deal[s];   // tile, wave, rank, first step in the region
+    const int32_t rb = tiles[dl.x].rb, t0 = rbt[rb], t1 = rbt[rb + 1];
+    const int64_t ra = ats_region(t0, t1, t0, dl.y, WAVES), r = ats_region(t0, t1, dl.x, dl.y, WAVES);
+    const int64_t q = (int64_t)rq[r] + dl.z;
+    const int64_t step0 = (int64_t)(rso[r] - rso[ra]) + dl.w;
+    const int64_t g0 = waves[(int64_t)rb * WAVES + dl.y].g0;
+    const uint32_t rl = srow[s * 64 + lane];
+    const int len = (int)(rl & ((1u << AT_LENBITS) - 1));
+    lword[q * 64 + lane] = rl;
+    if (lane == 0) recs[q] = make_int2((int)((uint32_t)sd.width | ((uint32_t)sd.wide << 31)), dl.x);
+    int64_t off = sd.base;
+    // the lanes with entries are a prefix, so step 0's entry of this lane is at base + lane
+    const uint16_t c0 = len > 0 ? pk[off + lane] : (uint16_t)0;
+    for (int k = 0; k < sd.width; ++k) {
+        uint16_t c = c0;
+        double v = ATS_DEFECT == 1 ? 1e-7 : 0.0;
+        if (k < len) {
+            c = pk[off + lane];
+            v = pv[off + lane];
+        }
+        off += __popcll(__ballot(k < len));
+        const int64_t st = step0 + k;
+        const int u = (int)(st & 3);
+        uint8_t *gp = stream + (g0 + (st >> 2)) * ATS_GBYTES;
+        *reinterpret_cast<double *>(gp + (u >> 1) * 1024 + lane * 16 + (u & 1) * 8) = v;
+        *reinterpret_cast<uint16_t *>(gp + 2048 + lane * 8 + u * 2) = c;
+    }
 }
 
 // grad = attr - F / Z (TsneHelpers.scala:311-317); MODE 0 writes it, MODE 1
@@ -2092,6 +2439,50 @@ static void build_attract_tiles(tsne_ctx *ctx, OptState *s) {
                 (long long)ncb, nt, ns, nsl, nsl ? (double)wsum / nsl : 0.0, (long long)wmax,
                 nsl ? (double)m / nsl : 0.0);
     }
+    // the stream layout (attract_tiles_stream): the 2-D non-loss launches'
+    // storage of the same slices -- the arrays above stay, for the loss launches
+    s->at_stream = false;
+    s->at_pad_ppm = 0;
+    if (ctx->opts.attract_stream && s->C == 2 && ctx->opts.attract_pipe == 0) {
+        constexpr int WV = ATCfg3::WAVES;
+        static_assert(ATCfg0::WAVES == WV && ATCfg1::WAVES == WV && ATCfg2::WAVES == WV, "one deal for every shape");
+        const int64_t nreg = (int64_t)nt * WV, nwv = nrb * WV;
+        int4 *deal = ws.get<int4>("opt.ats.deal", nsl);
+        int32_t *rcnt = ws.get<int32_t>("opt.ats.rcnt", nreg + 1), *rsteps = ws.get<int32_t>("opt.ats.rsteps", nreg + 1);
+        int32_t *rq = ws.get<int32_t>("opt.ats.rq", nreg + 1), *rso = ws.get<int32_t>("opt.ats.rso", nreg + 1);
+        TSNE_HIP(hipMemsetAsync(rcnt + nreg, 0, sizeof(int32_t), st));
+        TSNE_HIP(hipMemsetAsync(rsteps + nreg, 0, sizeof(int32_t), st));
+        hipLaunchKernelGGL(ats_deal<WV>, dim3(ceil_div(nt, 64)), dim3(64), 0, st, s->at_tiles, nt, s->at_slices,
+                           s->at_rbt, deal, rcnt, rsteps);
+        scan_i32(rcnt, rq, nreg + 1);
+        scan_i32(rsteps, rso, nreg + 1);
+        s->ats_waves = ws.get<AWave>("opt.ats.waves", nwv);
+        int32_t *wgroups = ws.get<int32_t>("opt.ats.wgroups", nwv), *wg0 = ws.get<int32_t>("opt.ats.wg0", nwv);
+        hipLaunchKernelGGL(ats_waves<WV>, dim3(ceil_div(nwv, 256)), dim3(256), 0, st, s->at_rbt, nrb, rq, rso,
+                           s->ats_waves, wgroups);
+        scan_i32(wgroups, wg0, nwv);
+        hipLaunchKernelGGL(ats_wave_g0, dim3(ceil_div(nwv, 256)), dim3(256), 0, st, s->ats_waves, wg0, nwv);
+        const int64_t groups = total(wg0, wgroups, nwv);
+        int32_t tsteps = 0;
+        TSNE_HIP(hipMemcpyAsync(&tsteps, rso + nreg, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TSNE_HIP(hipStreamSynchronize(st));
+        // the lane words are read two list slots ahead: slack
+        s->ats_stream = ws.get<uint8_t>("opt.ats.stream", (size_t)std::max<int64_t>(groups, 1) * ATS_GBYTES);
+        s->ats_recs = ws.get<int2>("opt.ats.recs", (size_t)nsl + 2);
+        s->ats_lword = ws.get<uint32_t>("opt.ats.lword", ((size_t)nsl + 2) * 64);
+        TSNE_HIP(hipMemsetAsync(s->ats_lword + (size_t)nsl * 64, 0, 2 * 64 * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(ats_fill<WV>, dim3(ceil_div(nsl, 4)), dim3(256), 0, st, s->at_slices, nsl, s->at_tiles,
+                           s->at_rbt, deal, rq, rso, s->ats_waves, s->at_srow, s->at_pk, s->at_pv, s->ats_recs,
+                           s->ats_lword, s->ats_stream);
+        TSNE_LAUNCH_CHECK();
+        s->at_pad_ppm = (int64_t)tsteps * 64 * 1000000 / m;   // stored slots per real entry
+        s->at_stream = true;
+        if (debug_tiles())
+            fprintf(stderr, "[attract stream] steps=%d groups=%lld stream=%.1f MB padding=%.4f (64 lanes a step; "
+                    "%.4f with the streams' last groups)\n", tsteps, (long long)groups,
+                    (double)groups * ATS_GBYTES / 1e6, (double)tsteps * 64 / (double)m,
+                    (double)groups * 256 / (double)m);
+    }
     s->at_nrb = nrb;
     s->at_ncb = ncb;
     s->at_rbs = rbs;
@@ -2565,6 +2956,14 @@ static void attract_tiles_launch_c(hipStream_t st, const OptState *s, const Attr
     hipLaunchKernelGGL(K, dim3(nb), dim3(CF::NT), 0, st, s->at_tiles, s->at_rbt, s->at_slices, s->at_srow,    \
                        a.r1 - a.r0, a.r0, s->n, s->at_pk, s->at_pv, a.Y, a.scal, a.ex, nb / NUM_XCD, a.attr, \
                        a.lpart, s->at_rbs)
+    if constexpr (!LOSS) {
+        if (s->at_stream) {   // built only with attract_pipe 0
+            hipLaunchKernelGGL((attract_tiles_stream<CF, MET>), dim3(nb), dim3(CF::NT), 0, st, s->at_tiles, s->at_rbt,
+                               s->ats_waves, s->ats_recs, s->ats_lword, s->ats_stream, a.r1 - a.r0, a.r0, s->n, a.Y,
+                               a.ex, nb / NUM_XCD, a.attr, s->at_rbs);
+            return;
+        }
+    }
     if constexpr (CF::RB == 4096 && !LOSS) {
         switch (s->at_pipe) {
             case 1: TSNE_ATP((attract_tiles_pipe<CF, 1, 6, LOSS, MET>)); return;
@@ -2810,6 +3209,11 @@ int64_t opt_attract_kernel(tsne_ctx *ctx) {
     OptState *s = ctx->opt;
     if (!s) return -1;
     return s->C == 3 ? (s->at_on ? 3 : 2) : (s->at_on ? 1 : 0);
+}
+
+int64_t opt_attract_pad(tsne_ctx *ctx) {
+    OptState *s = ctx->opt;
+    return (s && s->at_on && s->at_stream) ? s->at_pad_ppm : 0;
 }
 
 BHTree *opt_tree(tsne_ctx *ctx) {
