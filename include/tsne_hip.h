@@ -302,6 +302,9 @@ int tsne_ctx_loop_profile(tsne_ctx *ctx, char *buf, int64_t cap, int64_t *len_ou
  *   "opt.attract_kernel" the optimizer's attraction kernel: 0 attract_rows,
  *                        1 attract_tiles, 2 attract3 (3-D), 3 attract_tiles3
  *                        (3-D, tiled), -1 no optimizer;
+ *   "opt.attract_cfg"    the tiled layout's row-block configuration: 0..3 the
+ *                        2-D ATCfg0..3 (512 .. 4096 rows), 4 / 5 the 3-D
+ *                        2048- / 512-row blocks; -1 when the layout is off;
  *   "opt.attract_pad_ppm" the stream layout's stored slots per real entry,
  *                        in parts per million (>= 1000000; 0: not built);
  *   "opt.csort_oversized_total"  the same summed over every build of the optimizer's tree;

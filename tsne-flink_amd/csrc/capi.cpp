@@ -454,6 +454,7 @@ int tsne_ctx_counter(tsne_ctx *ctx, const char *name, int64_t *value_out) {
         else if (k == "opt.wave_mhz") *value_out = opt_wave_mhz(ctx);
         else if (k == "bh.csort_oversized") *value_out = ctx->single_tree ? csort_oversized(ctx, ctx->single_tree->cs) : 0;
         else if (k == "opt.attract_kernel") *value_out = opt_attract_kernel(ctx);
+        else if (k == "opt.attract_cfg") *value_out = opt_attract_cfg(ctx);
         else if (k == "opt.attract_pad_ppm") *value_out = opt_attract_pad(ctx);
         else if (k == "bh.spill_tasks" || k == "bh.spill_flags")
             *value_out = ctx->single_tree ? bh_spill_counter(ctx, *ctx->single_tree, k == "bh.spill_flags") : 0;

@@ -3211,6 +3211,11 @@ int64_t opt_attract_kernel(tsne_ctx *ctx) {
     return s->C == 3 ? (s->at_on ? 3 : 2) : (s->at_on ? 1 : 0);
 }
 
+int64_t opt_attract_cfg(tsne_ctx *ctx) {
+    OptState *s = ctx->opt;
+    return (s && s->at_on) ? s->at_cfg : -1;
+}
+
 int64_t opt_attract_pad(tsne_ctx *ctx) {
     OptState *s = ctx->opt;
     return (s && s->at_on && s->at_stream) ? s->at_pad_ppm : 0;
