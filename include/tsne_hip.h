@@ -513,7 +513,9 @@ int tsne_dev_opt_attract_log(tsne_ctx *ctx, int32_t *iters, int32_t *standalone,
  * their stream), in ms per interval since the stage was last reset:
  * "knn.filter" (the fp32-MFMA distance filter launches of the last kNN call),
  * "opt.attract" (see above), "opt.update" (combine + updateEmbedding +
- * centerEmbedding + write-back, per iteration).  *count = intervals. */
+ * centerEmbedding + write-back, per iteration), "pca.colmean", "pca.gram",
+ * "pca.reduce", "pca.project" (the kernels of the last tsne_[dev_]pca* call,
+ * one interval each).  *count = intervals. */
 int tsne_ctx_stage_ms(tsne_ctx *ctx, const char *stage, double *ms_out, int32_t cap, int32_t *count);
 
 /* ------------------------------------- embedding new points into a fitted map */
@@ -614,6 +616,56 @@ int tsne_transform_c(tsne_ctx *ctx, const tsne_params *params, const double *Yre
 int tsne_dev_transform_setup_c(tsne_ctx *ctx, const tsne_params *params, const double *d_Yref, int64_t n,
                                const int64_t *d_row_ptr, const int32_t *d_col, const double *d_P, int64_t m,
                                double *d_Y, double *d_upd, double *d_gains);
+
+/* ------------------------------------ principal components of the input rows */
+/* Not in the reference job: the usual companions of t-SNE, as the initial
+ * embedding and as the reduction of the input in front of the kNN.  For X
+ * (n x d, row-major):
+ *   mu_j = (1/n) sum_i X_ij;
+ *   C    = (1/n) sum_i (x_i - mu)(x_i - mu)^T, two-pass (rows centred before
+ *          the products), exactly symmetric;
+ *   lambda_1 >= lambda_2 >= ... the eigenvalues of C, v_a the unit
+ *          eigenvectors, each signed so that its coordinate of largest
+ *          absolute value is positive (ties: the lowest index);
+ *   scores = (X - mu) V^T (n x c_out): score (i, a) is the sequential sum over
+ *          j = 0..d-1 of (X_ij - mu_j) * V_aj, every product and sum rounded.
+ * All sums run in a fixed order that depends on n and d only (never on the
+ * device): a call repeated on the same data gives the same bits, and the host
+ * and device forms give the same bits.  The Gram matrix runs on the fp64 MFMA
+ * (DESIGN.md 3g); C crosses to the host for the eigen-solve (d <= 2048: at most
+ * 32 MB), so the device forms synchronise the stream.
+ * Errors: TSNE_ERR_ARG for n < 2, d < 1, c_out < 1, c_out > min(d, 64), c > d;
+ * TSNE_ERR_UNSUPPORTED for d > 2048 and for c other than 2 or 3.  On a
+ * tsne_ctx_create_multi handle these run on the first device. */
+
+/* All eigenpairs of the symmetric d x d matrix A (row-major; the lower
+ * triangle is read) on the host: Householder tridiagonalisation, then
+ * implicit-shift QL; single-threaded and deterministic.  evals_out[d]
+ * descending; evecs_out is d x d, row a = v_a with the sign rule above.  A
+ * non-finite entry or d < 1 is TSNE_ERR_ARG.  No context, no device. */
+int tsne_sym_eig(const double *A, int32_t d, double *evals_out, double *evecs_out);
+
+/* mean_out[d] and cov_out[d * d] = C. */
+int tsne_pca_covariance(tsne_ctx *ctx, const double *X, int64_t n, int32_t d, double *mean_out, double *cov_out);
+int tsne_dev_pca_covariance(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, double *d_mean, double *d_cov);
+
+/* The leading c_out principal components: mean_out[d], components_out
+ * [c_out * d] (row a = v_a), eigvals_out[c_out], scores_out[n * c_out].  Any
+ * output may be NULL (without scores_out no projection runs). */
+int tsne_pca(tsne_ctx *ctx, const double *X, int64_t n, int32_t d, int32_t c_out, double *mean_out,
+             double *components_out, double *eigvals_out, double *scores_out);
+int tsne_dev_pca(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t c_out, double *d_mean,
+                 double *d_components, double *d_eigvals, double *d_scores);
+
+/* PCA initialisation of the working set (instead of tsne_init_working_set):
+ * Y = scores[:, :c] * (1e-4 / sqrt(lambda_1)), upd = 0, gains = 1 (each n x c,
+ * c = 2 or 3).  The first column of Y has standard deviation 1e-4, the scale
+ * of initWorkingSet's N(0, 1e-4^2); no generator is involved.  lambda_1 <= 0
+ * (constant data) is TSNE_ERR_ARG. */
+int tsne_init_working_set_pca(tsne_ctx *ctx, const double *X, int64_t n, int32_t d, int32_t c, double *Y,
+                              double *upd, double *gains);
+int tsne_dev_init_working_set_pca(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t c, double *d_Y,
+                                  double *d_upd, double *d_gains);
 
 #ifdef __cplusplus
 }

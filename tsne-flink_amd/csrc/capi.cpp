@@ -11,6 +11,7 @@
 
 #include "bhtree.hpp"
 #include "common.hpp"
+#include "pca.hpp"
 #include "transform.hpp"
 
 namespace tsne {
@@ -1202,6 +1203,113 @@ int tsne_dev_transform_losses(tsne_ctx *ctx, int32_t *loss_keys, double *loss_va
         DeviceGuard g(ctx->device);
         const int32_t k = transform_losses(ctx, loss_keys, loss_vals, cap);
         if (n_loss) *n_loss = k;
+    });
+}
+
+// ------------------------------------------------ principal components (pca.hpp)
+
+int tsne_sym_eig(const double *A, int32_t d, double *evals_out, double *evecs_out) {
+    return guard([&] {
+        TSNE_REQUIRE(A && evals_out && evecs_out && d >= 1, "bad arguments");
+        const int rc = sym_eig(A, d, evals_out, evecs_out);
+        if (rc == 1) fail(TSNE_ERR_ARG, "the matrix has a non-finite entry");
+        if (rc != 0) fail(TSNE_ERR_HIP, "the eigen-solver did not converge");
+    });
+}
+
+// the host forms' input: validated before its size is used for the upload
+static double *upload_rows(tsne_ctx *ctx, const double *X, int64_t n, int32_t d) {
+    TSNE_REQUIRE(X != nullptr, "NULL buffer");
+    TSNE_REQUIRE(n >= 2, "PCA needs at least two rows");
+    TSNE_REQUIRE(d >= 1, "PCA needs at least one column");
+    return upload(ctx, "h.X", X, (size_t)n * (size_t)d);
+}
+
+int tsne_pca_covariance(tsne_ctx *ctx, const double *X, int64_t n, int32_t d, double *mean_out, double *cov_out) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        TSNE_REQUIRE(mean_out && cov_out, "NULL buffer");
+        if (d > PCA_MAX_D) fail(TSNE_ERR_UNSUPPORTED, "PCA supports at most 2048 columns");
+        double *dX = upload_rows(ctx, X, n, d);
+        double *dm = ctx->ws.get<double>("h.pca_mean", (size_t)d);
+        double *dc = ctx->ws.get<double>("h.pca_cov", (size_t)d * d);
+        pca_covariance_device(ctx, dX, n, d, dm, dc);
+        download(ctx, mean_out, dm, (size_t)d);
+        download(ctx, cov_out, dc, (size_t)d * d);
+        sync(ctx);
+    });
+}
+
+int tsne_dev_pca_covariance(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, double *d_mean, double *d_cov) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        pca_covariance_device(ctx, dX, n, d, d_mean, d_cov);
+    });
+}
+
+int tsne_pca(tsne_ctx *ctx, const double *X, int64_t n, int32_t d, int32_t c_out, double *mean_out,
+             double *components_out, double *eigvals_out, double *scores_out) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        double *dX = upload_rows(ctx, X, n, d);
+        TSNE_REQUIRE(c_out >= 1 && c_out <= std::min<int32_t>(d, PCA_MAX_OUT), "c_out must be in [1, min(d, 64)]");
+        double *dm = mean_out ? ctx->ws.get<double>("h.pca_mean", (size_t)d) : nullptr;
+        double *dv = components_out ? ctx->ws.get<double>("h.pca_comp", (size_t)c_out * d) : nullptr;
+        double *de = eigvals_out ? ctx->ws.get<double>("h.pca_eig", (size_t)c_out) : nullptr;
+        double *ds = scores_out ? ctx->ws.get<double>("h.pca_scores", (size_t)n * c_out) : nullptr;
+        pca_device(ctx, dX, n, d, c_out, dm, dv, de, ds);
+        if (mean_out) download(ctx, mean_out, dm, (size_t)d);
+        if (components_out) download(ctx, components_out, dv, (size_t)c_out * d);
+        if (eigvals_out) download(ctx, eigvals_out, de, (size_t)c_out);
+        if (scores_out) download(ctx, scores_out, ds, (size_t)n * c_out);
+        sync(ctx);
+    });
+}
+
+int tsne_dev_pca(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t c_out, double *d_mean,
+                 double *d_components, double *d_eigvals, double *d_scores) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        pca_device(ctx, dX, n, d, c_out, d_mean, d_components, d_eigvals, d_scores);
+    });
+}
+
+int tsne_init_working_set_pca(tsne_ctx *ctx, const double *X, int64_t n, int32_t d, int32_t c, double *Y,
+                              double *upd, double *gains) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        if (c != 2 && c != 3) fail(TSNE_ERR_UNSUPPORTED, "n_components must be 2 or 3");
+        TSNE_REQUIRE(Y && upd && gains, "NULL buffer");
+        double *dX = upload_rows(ctx, X, n, d);
+        const size_t ne = (size_t)n * (size_t)c;
+        double *dY = ctx->ws.get<double>("h.Y", ne + 1);
+        double *du = ctx->ws.get<double>("h.upd", ne + 1);
+        double *dn = ctx->ws.get<double>("h.gains", ne + 1);
+        pca_init_device(ctx, dX, n, d, c, dY, du, dn);
+        download(ctx, Y, dY, ne);
+        download(ctx, upd, du, ne);
+        download(ctx, gains, dn, ne);
+        sync(ctx);
+    });
+}
+
+int tsne_dev_init_working_set_pca(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t c, double *d_Y,
+                                  double *d_upd, double *d_gains) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        pca_init_device(ctx, dX, n, d, c, d_Y, d_upd, d_gains);
     });
 }
 

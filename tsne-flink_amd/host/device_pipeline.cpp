@@ -3,9 +3,12 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <chrono>
 #include <stdexcept>
 #include <string>
+
+#include "tsne_helpers.hpp"
 
 namespace tsne_flink {
 namespace {
@@ -34,20 +37,59 @@ double now() {
 }  // namespace
 
 DeviceRun runOnDevice(tsne_ctx *ctx, const std::vector<double> &X, int64_t n, int32_t d, int32_t k,
-                      double perplexity, const tsne_params &p, int64_t randomState) {
+                      double perplexity, const tsne_params &p, int64_t randomState, bool initPca,
+                      int32_t pcaDimension) {
     if (n < 2) throw std::invalid_argument("the device pipeline needs at least two points");
     DeviceRun out;
     const int64_t kk = std::min<int64_t>(k, n - 1);
     const int32_t C = p.n_components;
+    const size_t ne = (size_t)n * C;
     double t0 = now();
     // kNearestNeighbors (TsneHelpers.scala:41-59)
     DevArray<int32_t> idx((size_t)(n * kk));
     DevArray<double> dist((size_t)(n * kk));
+    DevArray<double> dY(ne), dU(ne), dG(ne);
     {
         DevArray<double> dX((size_t)n * d);
         hipCheck(hipMemcpy(dX.p, X.data(), sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice), "H2D X");
-        libCheck(tsne_dev_knn(ctx, dX.p, n, d, p.metric, k, 0, n, idx.p, dist.p));
-        libCheck(tsne_ctx_synchronize(ctx));
+        if (pcaDimension > 0) {
+            // the scores of the leading components in a second buffer; the kNN reads them
+            const int32_t cOut = std::max(pcaDimension, initPca ? C : 0);
+            DevArray<double> dS((size_t)n * cOut), dE((size_t)cOut);
+            libCheck(tsne_dev_pca(ctx, dX.p, n, d, cOut, nullptr, nullptr, dE.p, dS.p));
+            libCheck(tsne_ctx_synchronize(ctx));
+            dX.release();
+            if (initPca) {   // Y = scores[:, :C] * (1e-4 / sqrt(lambda_1)), as tsne_init_working_set_pca
+                double lambda1 = 0.0;
+                hipCheck(hipMemcpy(&lambda1, dE.p, sizeof(double), hipMemcpyDeviceToHost), "D2H lambda_1");
+                const double s = pcaInitScale(lambda1);
+                std::vector<double> y(ne), upd(ne, 0.0), gains(ne, 1.0);
+                hipCheck(hipMemcpy2D(y.data(), sizeof(double) * C, dS.p, sizeof(double) * cOut, sizeof(double) * C,
+                                     (size_t)n, hipMemcpyDeviceToHost), "D2H scores");
+                for (double &v : y) v = v * s;
+                hipCheck(hipMemcpy(dY.p, y.data(), sizeof(double) * ne, hipMemcpyHostToDevice), "H2D Y");
+                hipCheck(hipMemcpy(dU.p, upd.data(), sizeof(double) * ne, hipMemcpyHostToDevice), "H2D upd");
+                hipCheck(hipMemcpy(dG.p, gains.data(), sizeof(double) * ne, hipMemcpyHostToDevice), "H2D gains");
+            }
+            out.t_pca = now() - t0;
+            DevArray<double> dK(cOut == pcaDimension ? 0 : (size_t)n * pcaDimension);
+            const double *rows = dS.p;
+            if (cOut != pcaDimension) {   // fewer kNN columns than components: the leading ones, compact
+                hipCheck(hipMemcpy2D(dK.p, sizeof(double) * pcaDimension, dS.p, sizeof(double) * cOut,
+                                     sizeof(double) * pcaDimension, (size_t)n, hipMemcpyDeviceToDevice), "scores D2D");
+                rows = dK.p;
+            }
+            libCheck(tsne_dev_knn(ctx, rows, n, pcaDimension, p.metric, k, 0, n, idx.p, dist.p));
+            libCheck(tsne_ctx_synchronize(ctx));
+        } else {
+            if (initPca) {
+                libCheck(tsne_dev_init_working_set_pca(ctx, dX.p, n, d, C, dY.p, dU.p, dG.p));
+                libCheck(tsne_ctx_synchronize(ctx));
+                out.t_pca = now() - t0;
+            }
+            libCheck(tsne_dev_knn(ctx, dX.p, n, d, p.metric, k, 0, n, idx.p, dist.p));
+            libCheck(tsne_ctx_synchronize(ctx));
+        }
     }
     out.t_knn = now() - t0;
     t0 = now();
@@ -73,13 +115,13 @@ DeviceRun runOnDevice(tsne_ctx *ctx, const std::vector<double> &X, int64_t n, in
     out.t_aff = now() - t0;
     t0 = now();
     // initWorkingSet (:198-219) + optimize (:396-430), the state resident in HBM
-    const size_t ne = (size_t)n * C;
-    std::vector<double> y(ne), upd(ne), gains(ne);
-    libCheck(tsne_init_working_set(ctx, n, C, (uint64_t)randomState, y.data(), upd.data(), gains.data()));
-    DevArray<double> dY(ne), dU(ne), dG(ne);
-    hipCheck(hipMemcpy(dY.p, y.data(), sizeof(double) * ne, hipMemcpyHostToDevice), "H2D Y");
-    hipCheck(hipMemcpy(dU.p, upd.data(), sizeof(double) * ne, hipMemcpyHostToDevice), "H2D upd");
-    hipCheck(hipMemcpy(dG.p, gains.data(), sizeof(double) * ne, hipMemcpyHostToDevice), "H2D gains");
+    if (!initPca) {
+        std::vector<double> y(ne), upd(ne), gains(ne);
+        libCheck(tsne_init_working_set(ctx, n, C, (uint64_t)randomState, y.data(), upd.data(), gains.data()));
+        hipCheck(hipMemcpy(dY.p, y.data(), sizeof(double) * ne, hipMemcpyHostToDevice), "H2D Y");
+        hipCheck(hipMemcpy(dU.p, upd.data(), sizeof(double) * ne, hipMemcpyHostToDevice), "H2D upd");
+        hipCheck(hipMemcpy(dG.p, gains.data(), sizeof(double) * ne, hipMemcpyHostToDevice), "H2D gains");
+    }
     libCheck(tsne_dev_opt_setup(ctx, &p, prp.p, pcol.p, pval.p, n, dY.p, dU.p, dG.p));
     for (int32_t t = 1; t <= p.iterations; ++t) libCheck(tsne_dev_opt_step(ctx, t));
     libCheck(tsne_dev_opt_sync(ctx));

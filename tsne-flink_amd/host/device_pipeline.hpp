@@ -20,13 +20,21 @@ struct DeviceRun {
     std::map<int32_t, double> loss;    // the optimizer's "loss" accumulator
     int64_t nnz = 0;                   // entries of the joint distribution P
     double t_knn = 0, t_aff = 0, t_loop = 0;   // seconds, each stage to its completion
+    double t_pca = 0;                  // the PCA in front of the kNN and / or of the working set (part of t_knn)
 };
 
 // X: n x d row-major (rows = the sorted ids).  Exact kNN (k neighbours, as
 // TsneHelpers.kNearestNeighbors), affinities at `perplexity`, the joint P, the
 // working set initWorkingSet(randomState), then p.iterations of the optimizer.
 // Requires n >= 2 (every row then has k >= 1 neighbours: no empty row of P).
+// pcaDimension > 0: the kNN runs on the first pcaDimension principal-component
+// scores of X, written to a second HBM buffer (tsne_dev_pca), instead of on X.
+// initPca: the working set is the PCA initialisation of X instead of
+// initWorkingSet(randomState) -- with pcaDimension > 0 from the same scores
+// (one PCA of max(pcaDimension, n_components) components), else
+// tsne_dev_init_working_set_pca.
 DeviceRun runOnDevice(tsne_ctx *ctx, const std::vector<double> &X, int64_t n, int32_t d, int32_t k,
-                      double perplexity, const tsne_params &p, int64_t randomState);
+                      double perplexity, const tsne_params &p, int64_t randomState, bool initPca = false,
+                      int32_t pcaDimension = 0);
 
 }  // namespace tsne_flink

@@ -214,6 +214,59 @@ WorkingSet TsneHelpers::initWorkingSet(const std::vector<int32_t> &ids, int32_t 
     return w;
 }
 
+WorkingSet TsneHelpers::initWorkingSetPca(const std::vector<int32_t> &ids, const std::vector<double> &X, int32_t d,
+                                          int32_t nComponents) {
+    if (!std::is_sorted(ids.begin(), ids.end()) || X.size() != ids.size() * (size_t)std::max(d, 0))
+        throw std::invalid_argument("the PCA initialisation takes one input row per id, in ascending id order");
+    WorkingSet w;
+    w.ids = ids;
+    w.n_components = nComponents;
+    const size_t ne = w.ids.size() * (size_t)std::max(nComponents, 0);
+    w.y.resize(ne);
+    w.upd.resize(ne);
+    w.gains.resize(ne);
+    check(tsne_init_working_set_pca(ctx_, X.data(), (int64_t)ids.size(), d, nComponents, w.y.data(), w.upd.data(),
+                                    w.gains.data()));
+    return w;
+}
+
+PcaScores TsneHelpers::pca(const std::vector<double> &X, int64_t n, int32_t d, int32_t c_out) {
+    PcaScores r;
+    r.c_out = c_out;
+    r.eigvals.resize((size_t)std::max(c_out, 0));
+    r.scores.resize((size_t)std::max<int64_t>(n, 0) * (size_t)std::max(c_out, 0));
+    check(tsne_pca(ctx_, X.data(), n, d, c_out, nullptr, nullptr, r.eigvals.data(), r.scores.data()));
+    return r;
+}
+
+double pcaInitScale(double lambda1) {
+    if (!(lambda1 > 0.0)) throw std::invalid_argument("PCA initialisation of constant data (lambda_1 <= 0)");
+    return 1e-4 / std::sqrt(lambda1);
+}
+
+std::vector<double> leadingColumns(const std::vector<double> &rows, int64_t n, int32_t ld, int32_t cols) {
+    std::vector<double> out((size_t)n * (size_t)cols);
+    for (int64_t i = 0; i < n; ++i)
+        std::memcpy(&out[(size_t)i * cols], &rows[(size_t)i * ld], sizeof(double) * (size_t)cols);
+    return out;
+}
+
+WorkingSet workingSetFromScores(const std::vector<int32_t> &ids, const PcaScores &pca, int32_t nComponents) {
+    if (nComponents < 1 || nComponents > pca.c_out || pca.scores.size() != ids.size() * (size_t)pca.c_out)
+        throw std::invalid_argument("the scores do not hold nComponents columns for every id");
+    const double s = pcaInitScale(pca.eigvals[0]);
+    WorkingSet w;
+    w.ids = ids;
+    w.n_components = nComponents;
+    const size_t n = ids.size(), c = (size_t)nComponents;
+    w.y.resize(n * c);
+    w.upd.assign(n * c, 0.0);
+    w.gains.assign(n * c, 1.0);
+    for (size_t i = 0; i < n; ++i)
+        for (size_t k = 0; k < c; ++k) w.y[i * c + k] = pca.scores[i * (size_t)pca.c_out + k] * s;
+    return w;
+}
+
 std::vector<std::pair<int32_t, std::vector<double>>> TsneHelpers::gradient(const std::vector<Triple> &P,
                                                                          const WorkingSet &ws, int32_t metric,
                                                                          double theta, double exaggeration) {

@@ -43,8 +43,28 @@ struct Csr {
     std::vector<double> val;
 };
 
+// The leading principal components of the input rows (tsne_pca; not in the
+// reference job): what --pcaDimension and --init pca need of them.
+struct PcaScores {
+    int32_t c_out = 0;
+    std::vector<double> eigvals;   // c_out, descending
+    std::vector<double> scores;    // n x c_out, row-major
+};
+
 // Tsne.getMetric (Tsne.scala:161-168): the name validated, the id returned.
 int32_t getMetric(const std::string &name);
+
+// The factor of the PCA initialisation, 1e-4 / sqrt(lambda_1): the first
+// column of the working set then has standard deviation 1e-4.  lambda_1 <= 0
+// (constant data) throws std::invalid_argument, as tsne_init_working_set_pca
+// returns TSNE_ERR_ARG.
+double pcaInitScale(double lambda1);
+// The first `cols` columns of n x ld rows (row-major), compact.
+std::vector<double> leadingColumns(const std::vector<double> &rows, int64_t n, int32_t ld, int32_t cols);
+// The PCA initialisation from scores already computed: Y = scores[:, :c] *
+// pcaInitScale(lambda_1), upd = 0, gains = 1 -- the bits of
+// tsne_init_working_set_pca on the same rows (a score does not depend on c_out).
+WorkingSet workingSetFromScores(const std::vector<int32_t> &ids, const PcaScores &pca, int32_t nComponents);
 
 class TsneHelpers {
   public:
@@ -66,6 +86,12 @@ class TsneHelpers {
     std::vector<Triple> jointDistribution(const std::vector<Triple> &affinities);
     // TsneHelpers.scala:198-219 (randomState honoured: seeded generator)
     WorkingSet initWorkingSet(const std::vector<int32_t> &ids, int32_t nComponents, int64_t randomState);
+    // --init pca: the PCA initialisation of the rows X (ids.size() x d, rows in
+    // the order of the ascending ids) instead (tsne_init_working_set_pca)
+    WorkingSet initWorkingSetPca(const std::vector<int32_t> &ids, const std::vector<double> &X, int32_t d,
+                                 int32_t nComponents);
+    // --pcaDimension: eigenvalues and scores of the leading c_out components of X (n x d)
+    PcaScores pca(const std::vector<double> &X, int64_t n, int32_t d, int32_t c_out);
     // TsneHelpers.scala:221-318 (one evaluation; exaggeration multiplies P)
     std::vector<std::pair<int32_t, std::vector<double>>> gradient(const std::vector<Triple> &P,
                                                                   const WorkingSet &embedding,

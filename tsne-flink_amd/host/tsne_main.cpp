@@ -8,7 +8,17 @@
 //            [--randomState 0] [--neighbors 3*perplexity] [--initialMomentum 0.5]
 //            [--finalMomentum 0.8] [--theta 0.25] [--loss loss.txt | --lossFile loss.txt]
 //            [--knnIterations 3] [--knnBlocks P] [--inputDistanceMatrix] [--executionPlan]
-//            [--device 0] [--hostChain]
+//            [--device 0] [--hostChain] [--init random|pca] [--pcaDimension 0]
+// Beyond the reference's flags: --init pca starts from the PCA initialisation
+// of the input rows (tsne_init_working_set_pca; --randomState is then unused)
+// instead of the seeded N(0, 1e-4^2); --pcaDimension p > 0 runs the kNN on the
+// first p principal-component scores instead of the raw rows.  The metric then
+// applies to the scores: sqeuclidean / euclidean on all d scores would equal
+// those on X, on p < d they drop the trailing components; cosine on the
+// (centred) scores is NOT cosine on X.  Refused (IllegalArgumentException):
+// --pcaDimension with --knnMethod project (its Z-order comparator is a total
+// order only for nonnegative inputs; scores are signed), either flag with
+// --inputDistanceMatrix (no rows), p > min(dimension, 64).
 // The exact kNN methods run kNN -> affinities -> joint -> optimize resident
 // in HBM (device_pipeline.hpp); --hostChain (and --knnMethod project, the
 // distance-matrix input) take the TsneHelpers mirror, whose operators pass
@@ -105,6 +115,20 @@ int main(int argc, char **argv) {
         const int device = (int)parameters.getLong("device", 0);
         const long knnIterations = parameters.getLong("knnIterations", 3);
         (void)parameters.getLong("knnBlocks", 1);
+        const std::string initMethod = parameters.get("init", "random");
+        const long pcaDimension = parameters.getLong("pcaDimension", 0);
+        if (initMethod != "random" && initMethod != "pca")
+            throw std::invalid_argument("Init method '" + initMethod + "' not defined");
+        const bool initPca = initMethod == "pca";
+        if (pcaDimension < 0) throw std::invalid_argument("pcaDimension must not be negative");
+        if ((initPca || pcaDimension > 0) && inputDistanceMatrix)
+            throw std::invalid_argument("--init pca and --pcaDimension need the input rows, not a distance matrix");
+        if (pcaDimension > 0 && knnMethod == "project")
+            throw std::invalid_argument("--pcaDimension with --knnMethod project: the Z-order needs nonnegative inputs");
+        if (pcaDimension > std::min<long>(inputDimension, 64))
+            throw std::invalid_argument("pcaDimension exceeds min(dimension, 64)");
+        if (initPca && nComponents > inputDimension)
+            throw std::invalid_argument("--init pca: nComponents exceeds the input's dimension");
 
         if (getExecutionPlan) {  // Tsne.scala:89-95: write the plan instead of executing
             std::ofstream pw("tsne_executionPlan.json");
@@ -135,12 +159,13 @@ int main(int argc, char **argv) {
         // from the GPU's output on (no 10^8-element triple vectors)
         Csr knn;
         bool done = false;
+        std::vector<double> X;     // the input rows (kept for the host chain's --init pca)
+        PcaScores pcaScores;       // --pcaDimension on the host chain
         if (inputDistanceMatrix) {
             knn = toCsr(readDistanceMatrix(inputPath));
         } else {
             // Tsne.readInput's rows, ordered by id as the kNN takes them (readInputDense)
             std::vector<int32_t> ids;
-            std::vector<double> X;
             readInputDense(inputPath, inputDimension, ids, X);
             double t1 = now();
             std::fprintf(stderr, "[tsne_hip] read %zu points in %.3f s\n", ids.size(), t1 - t0);
@@ -150,7 +175,8 @@ int main(int argc, char **argv) {
                 // the exact kNN methods: the whole chain resident in HBM (device_pipeline.hpp);
                 // --hostChain runs the TsneHelpers mirror's host round trips instead
                 DeviceRun run = runOnDevice(h.context(), X, (int64_t)ids.size(), inputDimension, (int32_t)neighbors,
-                                            perplexity, prm, randomState);
+                                            perplexity, prm, randomState, initPca, (int32_t)pcaDimension);
+                if (initPca || pcaDimension > 0) std::fprintf(stderr, "[tsne_hip] PCA in %.3f s\n", run.t_pca);
                 std::fprintf(stderr, "[tsne_hip] kNN in %.3f s\n", run.t_knn);
                 std::fprintf(stderr, "[tsne_hip] affinities + joint in %.3f s (nnz %lld)\n", run.t_aff,
                              (long long)run.nnz);
@@ -160,11 +186,22 @@ int main(int argc, char **argv) {
                 ws.y = std::move(run.y);
                 loss = std::move(run.loss);
                 done = true;
+            } else if (pcaDimension > 0) {
+                // one PCA serves the kNN's input and, with --init pca, the working set
+                const int32_t cOut = (int32_t)std::max(pcaDimension, initPca ? nComponents : 0L);
+                pcaScores = h.pca(X, (int64_t)ids.size(), inputDimension, cOut);
+                std::fprintf(stderr, "[tsne_hip] PCA in %.3f s\n", now() - t1);
+                const std::vector<double> S = leadingColumns(pcaScores.scores, (int64_t)ids.size(), cOut,
+                                                             (int32_t)pcaDimension);
+                knn = h.kNearestNeighborsCsr(std::move(ids), S, (int32_t)pcaDimension, (int32_t)neighbors, metric,
+                                             knnMethod, (int32_t)knnIterations, randomState);
+                std::fprintf(stderr, "[tsne_hip] kNN in %.3f s\n", now() - t1);
             } else {
                 knn = h.kNearestNeighborsCsr(std::move(ids), X, inputDimension, (int32_t)neighbors, metric, knnMethod,
                                              (int32_t)knnIterations, randomState);
                 std::fprintf(stderr, "[tsne_hip] kNN in %.3f s\n", now() - t1);
             }
+            if (done || !initPca || pcaDimension > 0) std::vector<double>().swap(X);   // only the host chain's PCA start reads the rows again
         }
         if (!done) {
             double t2 = now();
@@ -181,7 +218,16 @@ int main(int argc, char **argv) {
                 }
             }
             std::fprintf(stderr, "[tsne_hip] affinities + joint in %.3f s (nnz %zu)\n", now() - t2, P.val.size());
-            ws = h.initWorkingSet(P.ids, (int32_t)nComponents, randomState);
+            if (initPca) {
+                // the rows of P are the input's rows (every point has a neighbour), so the
+                // working set is the PCA initialisation of the input, row for row
+                if (pcaDimension == 0 && P.ids.size() * (size_t)inputDimension != X.size())
+                    throw std::invalid_argument("--init pca: a point of the input has no entry in P");
+                ws = pcaDimension > 0 ? workingSetFromScores(P.ids, pcaScores, (int32_t)nComponents)
+                                      : h.initWorkingSetPca(P.ids, X, inputDimension, (int32_t)nComponents);
+            } else {
+                ws = h.initWorkingSet(P.ids, (int32_t)nComponents, randomState);
+            }
             double t3 = now();
             h.optimizeCsr(P, ws, learningRate, (int32_t)iterations, metric, earlyExaggeration, initialMomentum,
                           finalMomentum, theta, &loss);

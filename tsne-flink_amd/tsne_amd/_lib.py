@@ -101,6 +101,13 @@ SIGNATURES = {
     "tsne_dev_transform_step": (C.c_int, [P, I32]),
     "tsne_dev_transform_sync": (C.c_int, [P]),
     "tsne_dev_transform_losses": (C.c_int, [P, P, P, I32, PI32]),
+    "tsne_sym_eig": (C.c_int, [P, I32, P, P]),
+    "tsne_pca_covariance": (C.c_int, [P, P, I64, I32, P, P]),
+    "tsne_dev_pca_covariance": (C.c_int, [P, P, I64, I32, P, P]),
+    "tsne_pca": (C.c_int, [P, P, I64, I32, I32, P, P, P, P]),
+    "tsne_dev_pca": (C.c_int, [P, P, I64, I32, I32, P, P, P, P]),
+    "tsne_init_working_set_pca": (C.c_int, [P, P, I64, I32, I32, P, P, P]),
+    "tsne_dev_init_working_set_pca": (C.c_int, [P, P, I64, I32, I32, P, P, P]),
 }
 
 _lib = None

@@ -307,6 +307,57 @@ class Context:
         check(lib().tsne_init_working_set(self._h, n, n_components, seed, _ptr(Y), _ptr(upd), _ptr(gains)))
         return Y, upd, gains
 
+    # ---- principal components of the input rows (include/tsne_hip.h "principal components")
+    def pcaCovariance(self, X):
+        """tsne_pca_covariance -> (mean[d], C[d, d]); C = (1/n) sum (x - mean)(x - mean)^T."""
+        X = _f64(X)
+        n, d = X.shape
+        mean = np.zeros(d)
+        cov = np.zeros((d, d))
+        check(lib().tsne_pca_covariance(self._h, _ptr(X), n, d, _ptr(mean), _ptr(cov)))
+        return mean, cov
+
+    def pca(self, X, n_components):
+        """tsne_pca -> (scores[n, c], components[c, d], eigvals[c], mean[d]):
+        eigenvalues descending, each component's largest coordinate positive."""
+        X = _f64(X)
+        n, d = X.shape
+        c = int(n_components)
+        shape = lambda *s: np.zeros([max(int(v), 0) for v in s])   # noqa: E731 -- bad sizes reach the library's check
+        scores, comp, eig, mean = shape(n, c), shape(c, d), shape(c), shape(d)
+        check(lib().tsne_pca(self._h, _ptr(X), n, d, c, _ptr(mean), _ptr(comp), _ptr(eig), _ptr(scores)))
+        return scores, comp, eig, mean
+
+    def initWorkingSetPCA(self, X, n_components=2):
+        """tsne_init_working_set_pca -> (Y, upd, gains): the first n_components
+        scores scaled so that Y[:, 0] has standard deviation 1e-4."""
+        X = _f64(X)
+        n, d = X.shape
+        Y = np.zeros((n, n_components))
+        upd = np.zeros_like(Y)
+        gains = np.zeros_like(Y)
+        check(lib().tsne_init_working_set_pca(self._h, _ptr(X), n, d, n_components, _ptr(Y), _ptr(upd), _ptr(gains)))
+        return Y, upd, gains
+
+    def dev_pca_covariance(self, dX, d_mean, d_cov):
+        self._fence(dX)
+        n, d = dX.shape
+        check(lib().tsne_dev_pca_covariance(self._h, _ptr(dX), n, d, _ptr(d_mean), _ptr(d_cov)))
+
+    def dev_pca(self, dX, n_components, d_mean=None, d_components=None, d_eigvals=None, d_scores=None):
+        """tsne_dev_pca on torch tensors; outputs that are None are not produced.
+        Returns after the stream has been synchronised (the eigen-solve is on the host)."""
+        self._fence(dX)
+        n, d = dX.shape
+        check(lib().tsne_dev_pca(self._h, _ptr(dX), n, d, n_components, _ptr(d_mean), _ptr(d_components),
+                                 _ptr(d_eigvals), _ptr(d_scores)))
+
+    def dev_init_working_set_pca(self, dX, dY, dupd, dgains):
+        self._fence(dX)
+        n, d = dX.shape
+        check(lib().tsne_dev_init_working_set_pca(self._h, _ptr(dX), n, d, dY.shape[1], _ptr(dY), _ptr(dupd),
+                                                  _ptr(dgains)))
+
     def optimize(self, row_ptr, col, P, Y, upd, gains, params):
         """TsneHelpers.scala:396-430, in place; returns {iteration: loss}."""
         n = Y.shape[0]
@@ -539,6 +590,19 @@ def transform(ctx, X_ref, Y_ref, X_new, k, perplexity, metric="sqeuclidean", par
     upd, gains = np.zeros_like(Y), np.ones_like(Y)
     losses = ctx.transform(Y_ref, rp, idx.ravel(), P, Y, upd, gains, params)
     return Y, losses
+
+
+def sym_eig(A):
+    """tsne_sym_eig: all eigenpairs of a symmetric matrix on the host ->
+    (eigvals[d] descending, eigvecs[d, d] with row a the vector of eigvals[a])."""
+    A = _f64(A)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("A must be square, got shape %s" % (A.shape,))
+    d = A.shape[0]
+    w = np.zeros(d)
+    V = np.zeros((d, d))
+    check(lib().tsne_sym_eig(_ptr(A), d, _ptr(w), _ptr(V)))
+    return w, V
 
 
 def project_shifts(iterations, d, seed=0):
