@@ -190,6 +190,11 @@ int tsne_ctx_synchronize(tsne_ctx *ctx);
  *                             default: measured slower at C3).
  *                             trav_prio 1-3: the 64-query traversal's waves at
  *                             that issue priority (no measured effect);
+ *   "trav_burst" 1            the 64-query BH traversal (2-D) reads a popped
+ *                             record's fields from LDS in bursts: the head's
+ *                             at once, each child's while the child before it
+ *                             is evaluated (0: one by one, at first use; the
+ *                             same bits; not the tree partition's walks);
  *   "trav_front" 0             > 0: the 64-query traversal's workgroups whose
  *                             heaviest wave cost >= this x the previous
  *                             traversal's mean are dispatched first (the order

@@ -656,14 +656,37 @@ struct TravLDS_T {
 using TravLDS = TravLDS_T<4, TRAV_WPB>;
 using NarrowLDS = TravLDS_T<(NKP > 4 ? NKP : 4)>;
 
+// The LDS copy of a popped record under option trav_burst: QRec's 8-byte
+// pieces regrouped so that what one step of a pop needs lies in whole 16-byte
+// pieces -- the four words and {ex, lmask} the pop starts from, and per child
+// {ccx, ccy} and {cb, ca} -- read with one ds_read_b128 each (RecHead,
+// RecChild).  QRec itself (HBM; build_qrec, the narrow kernel, transform.hip)
+// is unchanged: stage_records<., true> permutes while staging.
+struct __attribute__((aligned(16))) QRecB {
+    double cx, cy, rball, hmin, bx0, bx1, by0, by1;
+    int32_t first, last, cnt, nch;
+    double ex;
+    uint64_t lmask;
+    struct { double ccx, ccy, cb, ca; } ch[4];
+    int32_t cref[4], ccnt[4];
+};
+static_assert(sizeof(QRecB) == sizeof(QRec) && offsetof(QRecB, first) == offsetof(QRec, first) &&
+              offsetof(QRecB, ch) == 96 && offsetof(QRecB, cref) == 224, "QRecB: a permutation of QRec's pieces");
+
 // Stage the records of stack entries [sp, sp + k) of wave w into LDS (one
 // round of coalesced 16-byte loads; their latencies overlap), each with its
 // entry's lane mask in the copy's lmask slot (read with the record's other
-// fields from one LDS address).
-template <class LDS>
+// fields from one LDS address).  BURST: in QRecB's order (each lane's two
+// 8-byte halves to their places).
+template <class LDS, bool BURST = false>
 __device__ __forceinline__ void stage_records(LDS &L, int w, int lane, int sp, int k,
                                               const QRec *__restrict__ qrec) {
+    // (BURST: the lane's addresses are recomputed per batch, a few VALU, instead of
+    // living in ~10 VGPRs across the pop loop, which needs them for the bursts)
+    if (BURST) asm volatile("" : "+v"(lane));
     static_assert(offsetof(QRec, lmask) == 16 * (QREC_V4 - 1) + 8, "lmask: the upper half of the last 16 bytes");
+    static_assert(!BURST || (QREC_V4 == 16 && offsetof(QRec, ccx) == 80 && offsetof(QRec, cref) == 208 &&
+                             offsetof(QRec, ex) == 240), "the permutation below is QRec's layout");
     if (lane < k) L.bref[w][lane] = L.sref[w][sp + lane];
     for (int e = lane; e < QREC_V4 * k; e += 64) {
         const int rr = e / QREC_V4, part = e - rr * QREC_V4;
@@ -674,12 +697,138 @@ __device__ __forceinline__ void stage_records(LDS &L, int w, int lane, int sp, i
             v.z = (uint32_t)m;
             v.w = (uint32_t)(m >> 32);
         }
-        reinterpret_cast<uint4 *>(&L.srec[w][rr])[part] = v;
+        if (BURST) {
+            // halves 2 part, 2 part + 1 of QRec -> halves d0, d1 of QRecB
+            int d0 = 2 * part, d1 = d0 + 1;                   // the tile fields, first .. nch: in place
+            if (part >= 5 && part < 13) {                     // ccx, ccy, cb, ca [c, c + 1] -> ch[c], ch[c + 1]
+                const int j = 2 * part - 10;
+                d0 = 12 + 4 * (j & 3) + (j >> 2);
+                d1 = d0 + 4;
+            } else if (part >= 13) {                          // cref, ccnt: one piece on; {ex, lmask}: piece 5
+                d0 = part == 15 ? 10 : 2 * part + 2;
+                d1 = d0 + 1;
+            }
+            uint64_t *dst = reinterpret_cast<uint64_t *>(&L.srec[w][rr]);
+            dst[d0] = ((uint64_t)v.y << 32) | v.x;
+            dst[d1] = ((uint64_t)v.w << 32) | v.z;
+        } else {
+            reinterpret_cast<uint4 *>(&L.srec[w][rr])[part] = v;
+        }
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0);   // vmcnt = lgkmcnt = 0: batch staged in LDS
     __builtin_amdgcn_wave_barrier();
 }
+
+// The fields of a popped record as the 64-query pop loop reads them (option
+// trav_burst).  <false>: in place, each at its first use (the compiler waits
+// for every LDS round trip where its value is needed: a chain of ~10 per
+// pop).  <true>: fetch() issues all reads of a step at once, from the QRecB
+// copy, in the order their values are needed; LDS returns in order, so the
+// waits the compiler places are partial counts and one round trip covers the
+// step.  The loads are volatile so that they stay where they are issued; the
+// values, and everything computed from them, are the same.
+typedef double f64x2_t __attribute__((ext_vector_type(2)));
+typedef int32_t i32x4_t __attribute__((ext_vector_type(4)));
+typedef uint64_t u64x2_t __attribute__((ext_vector_type(2)));
+template <class T> __device__ __forceinline__ T lds_fetch(const void *p) {
+    typedef const volatile __attribute__((address_space(3))) T *lds_ptr;
+    return *(lds_ptr)(const __attribute__((address_space(3))) void *)p;
+}
+template <bool BURST> struct RecHead;
+template <> struct RecHead<false> {
+    const QRec *nd;
+    const int32_t *br;
+    __device__ __forceinline__ void fetch(const QRec *rec, const int32_t *bref) { nd = rec; br = bref; }
+    __device__ __forceinline__ int32_t ref() const { return *br; }
+    __device__ __forceinline__ uint64_t lmask() const { return nd->lmask; }
+    __device__ __forceinline__ int32_t nch() const { return nd->nch; }
+    __device__ __forceinline__ int32_t first() const { return nd->first; }
+    __device__ __forceinline__ int32_t last() const { return nd->last; }
+    __device__ __forceinline__ int32_t cnt() const { return nd->cnt; }
+    __device__ __forceinline__ double cx() const { return nd->cx; }
+    __device__ __forceinline__ double cy() const { return nd->cy; }
+    __device__ __forceinline__ double rball() const { return nd->rball; }
+    __device__ __forceinline__ double hmin() const { return nd->hmin; }
+    __device__ __forceinline__ double bx0() const { return nd->bx0; }
+    __device__ __forceinline__ double bx1() const { return nd->bx1; }
+    __device__ __forceinline__ double by0() const { return nd->by0; }
+    __device__ __forceinline__ double by1() const { return nd->by1; }
+    __device__ __forceinline__ double ex() const { return nd->ex; }
+};
+template <> struct RecHead<true> {
+    i32x4_t ids;     // first, last, cnt, nch
+    u64x2_t em;      // ex (bits), lmask
+    int32_t rf;
+    f64x2_t c, rh, bx, by;
+    // the three words the pop's scalar state comes from first, then the tile test's
+    __device__ __forceinline__ void fetch(const QRec *rec, const int32_t *bref) {
+        const QRecB *b = reinterpret_cast<const QRecB *>(rec);
+        ids = lds_fetch<i32x4_t>(&b->first);
+        em = lds_fetch<u64x2_t>(&b->ex);
+        rf = lds_fetch<int32_t>(bref);
+        c = lds_fetch<f64x2_t>(&b->cx);
+        rh = lds_fetch<f64x2_t>(&b->rball);
+        bx = lds_fetch<f64x2_t>(&b->bx0);
+        by = lds_fetch<f64x2_t>(&b->by0);
+    }
+    __device__ __forceinline__ int32_t ref() const { return rf; }
+    __device__ __forceinline__ uint64_t lmask() const { return em.y; }
+    __device__ __forceinline__ int32_t nch() const { return ids.w; }
+    __device__ __forceinline__ int32_t first() const { return ids.x; }
+    __device__ __forceinline__ int32_t last() const { return ids.y; }
+    __device__ __forceinline__ int32_t cnt() const { return ids.z; }
+    __device__ __forceinline__ double cx() const { return c.x; }
+    __device__ __forceinline__ double cy() const { return c.y; }
+    __device__ __forceinline__ double rball() const { return rh.x; }
+    __device__ __forceinline__ double hmin() const { return rh.y; }
+    __device__ __forceinline__ double bx0() const { return bx.x; }
+    __device__ __forceinline__ double bx1() const { return bx.y; }
+    __device__ __forceinline__ double by0() const { return by.x; }
+    __device__ __forceinline__ double by1() const { return by.y; }
+    __device__ __forceinline__ double ex() const { return __longlong_as_double((long long)em.x); }
+};
+// Child c's fields: <true> its bundle in one burst (fetched while the child
+// before it is evaluated); at(): in place, for the rare kinds' loop.
+template <bool BURST> struct RecChild;
+template <> struct RecChild<false> {
+    const QRec *nd;
+    int c;
+    __device__ __forceinline__ void fetch(const QRec *rec, int cc) { nd = rec; c = cc; }
+    __device__ __forceinline__ double ccx() const { return nd->ccx[c]; }
+    __device__ __forceinline__ double ccy() const { return nd->ccy[c]; }
+    __device__ __forceinline__ double cb() const { return nd->cb[c]; }
+    __device__ __forceinline__ double ca() const { return nd->ca[c]; }
+    __device__ __forceinline__ int32_t ccnt() const { return nd->ccnt[c]; }
+    __device__ __forceinline__ int32_t cref() const { return nd->cref[c]; }
+};
+// (in place in either layout: the rare kinds' loop)
+template <bool BURST> struct RecChildAt {
+    const QRec *nd;
+    int c;
+    __device__ __forceinline__ const QRecB *b() const { return reinterpret_cast<const QRecB *>(nd); }
+    __device__ __forceinline__ double ccx() const { return BURST ? b()->ch[c].ccx : nd->ccx[c]; }
+    __device__ __forceinline__ double ccy() const { return BURST ? b()->ch[c].ccy : nd->ccy[c]; }
+    __device__ __forceinline__ int32_t ccnt() const { return BURST ? b()->ccnt[c] : nd->ccnt[c]; }
+    __device__ __forceinline__ int32_t cref() const { return BURST ? b()->cref[c] : nd->cref[c]; }
+};
+template <> struct RecChild<true> {
+    f64x2_t p, ba;
+    int32_t n, rf;
+    __device__ __forceinline__ void fetch(const QRec *rec, int cc) {
+        const QRecB *b = reinterpret_cast<const QRecB *>(rec);
+        p = lds_fetch<f64x2_t>(&b->ch[cc].ccx);
+        ba = lds_fetch<f64x2_t>(&b->ch[cc].cb);
+        n = lds_fetch<int32_t>(&b->ccnt[cc]);
+        rf = lds_fetch<int32_t>(&b->cref[cc]);
+    }
+    __device__ __forceinline__ double ccx() const { return p.x; }
+    __device__ __forceinline__ double ccy() const { return p.y; }
+    __device__ __forceinline__ double cb() const { return ba.x; }
+    __device__ __forceinline__ double ca() const { return ba.y; }
+    __device__ __forceinline__ int32_t ccnt() const { return n; }
+    __device__ __forceinline__ int32_t cref() const { return rf; }
+};
 
 // The half width of cell child `cref` of record `ref` (flags stripped), for
 // the exact-quotient band (QACC_BAND): a real node's own h, or for the
@@ -1214,7 +1363,10 @@ __device__ __forceinline__ void sp_write(const SpillView &sv, LDS &L, int w, int
 // hands the rest to the task queue; TASK: the drain launches' instantiation,
 // whose waves take tasks while the queue has any (see "Spill" above) -- a
 // kernel of its own, so that the 64-query walk keeps its registers.
-template <int MODE, bool PART, bool TASK>
+// BURST (option trav_burst): a popped record's fields are read in bursts
+// (RecHead, RecChild) instead of one by one; the tree partition's
+// instantiations keep the reads in place (their slow path reads QRec's layout).
+template <int MODE, bool PART, bool TASK, bool BURST = false>
 __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(8))) void bh_traverse(
     const double2 *__restrict__ pos, const int32_t *__restrict__ dupc, const BHNode *__restrict__ nodes,
     const QRec *__restrict__ qrec, TileTask *__restrict__ ttask, int32_t *__restrict__ ttask_n,
@@ -1224,6 +1376,7 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(8
     int32_t *__restrict__ tcost, const int32_t *__restrict__ cost_lab, NarrowView nv, int32_t *__restrict__ plim,
     SpillView sv, StreamView stv) {
     constexpr bool STATS = MODE == 2, COST = MODE >= 1;
+    static_assert(!(PART && BURST), "the tree partition's slow path reads QRec's own layout");
     if (!PART && !TASK && stv.prio > 0) {   // issue priority over the waves beside it (option trav_prio)
         if (stv.prio == 1) __builtin_amdgcn_s_setprio(1);
         else if (stv.prio == 2) __builtin_amdgcn_s_setprio(2);
@@ -1304,14 +1457,22 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(8
         }
         const int kb = sp > STACK / 2 ? 1 : (sp < 4 ? sp : 4);
         sp -= kb;
-        stage_records(L, w, lane, sp, kb, qrec);
+        stage_records<TravLDS, BURST>(L, w, lane, sp, kb, qrec);
         const QRec *brec = L.srec[w];
         const int32_t *bref_c = L.bref[w];
         npops += kb;
         for (int r = 0; r < kb; ++r) {
             if (STATS) ++wpops;
-            const int ref = __builtin_amdgcn_readfirstlane(bref_c[r]);
-            const uint64_t msk = brec[r].lmask;
+            // the record's head fields; BURST: with child 0's, in one burst
+            RecHead<BURST> hd;
+            RecChild<BURST> chs[4];   // (one per unrolled child slot: registers, no copies)
+            hd.fetch(brec + r, bref_c + r);
+            if (BURST) {
+                chs[0].fetch(brec + r, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const int ref = __builtin_amdgcn_readfirstlane(hd.ref());
+            const uint64_t msk = hd.lmask();
             const uint64_t msk_s = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(msk >> 32)) << 32) |
                                    (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)msk);   // the wave's (scalar)
             bool act = __builtin_amdgcn_inverse_ballot_w64(msk_s);   // the mask's own SGPRs: no VALU
@@ -1406,15 +1567,15 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(8
             // read the mask's SGPRs directly: no VALU per conversion.
             uint64_t tm = 0;
             uint64_t amask = msk_s;
-            const int nflags = __builtin_amdgcn_readfirstlane(nd.nch);   // the record is the wave's
+            const int nflags = __builtin_amdgcn_readfirstlane(hd.nch());   // the record is the wave's
             if (nflags & QNCH_TILE) {
-                const double cdx = qx - nd.cx, cdy = qy - nd.cy;
-                const double ex = __fma_rn(1e-15, qmag, nd.ex);
-                const double dxm = fmax(fabs(qx - nd.bx0), fabs(qx - nd.bx1)) + ex;
-                const double dym = fmax(fabs(qy - nd.by0), fabs(qy - nd.by1)) + ex;
+                const double cdx = qx - hd.cx(), cdy = qy - hd.cy();
+                const double ex = __fma_rn(1e-15, qmag, hd.ex());
+                const double dxm = fmax(fabs(qx - hd.bx0()), fabs(qx - hd.bx1())) + ex;
+                const double dym = fmax(fabs(qy - hd.by0()), fabs(qy - hd.by1())) + ex;
                 // (FMA forms: the bounds carry 1e-9 / 1.1e-12 relative margins)
-                tm = msk_s & (__builtin_amdgcn_ballot_w64(__fma_rn(cdx, cdx, cdy * cdy) <= nd.rball) |
-                              __builtin_amdgcn_ballot_w64(__fma_rn(dxm, dxm, dym * dym) <= nd.hmin));
+                tm = msk_s & (__builtin_amdgcn_ballot_w64(__fma_rn(cdx, cdx, cdy * cdy) <= hd.rball()) |
+                              __builtin_amdgcn_ballot_w64(__fma_rn(dxm, dxm, dym * dym) <= hd.hmin()));
             }
             if (!PART && tm && task && ntt == tcap) {   // a task's tile page is full (or none yet): the next one
                 if (page >= 0 && lane == 0) { sv.pg_n[page] = ntt; sv.pg_grp[page] = (int32_t)grp; }
@@ -1438,9 +1599,9 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(8
                 // The range holds whole equal-key runs, so either all of the
                 // query's exact duplicates (itself included) are in it or none
                 // is; they add exactly 1 each to z in the leaf sum: taken off here.
-                const int a = __builtin_amdgcn_readfirstlane(nd.first), b = __builtin_amdgcn_readfirstlane(nd.last);
+                const int a = __builtin_amdgcn_readfirstlane(hd.first()), b = __builtin_amdgcn_readfirstlane(hd.last());
                 if (lane == 0) {
-                    TileTask tt; tt.ref = ref; tt.first = a; tt.last = b; tt.pad = nd.cnt; tt.mask = tm;
+                    TileTask tt; tt.ref = ref; tt.first = a; tt.last = b; tt.pad = hd.cnt(); tt.mask = tm;
                     tdst[ntt] = tt;
                 }
                 ++ntt;
@@ -1461,6 +1622,19 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(8
             for (int c = 0; c < 4; ++c) {
                 if (c >= nch) break;
                 const int kind = (nflags >> (QNCH_KIND + 2 * c)) & 3;   // uniform: scalar branches
+                // BURST: this child's bundle was fetched while the one before it was
+                // evaluated (child 0's with the head); the next slot's goes out now,
+                // ahead of this child's arithmetic.  It goes out whether or not the
+                // record has a child there (a read inside the record, never used):
+                // under `c + 1 < nch` the compiler kept all four bundles live as
+                // partly defined values and spilled them (172 bytes of scratch).
+                if (BURST) {
+                    if (c + 1 < 4) chs[c + 1 < 4 ? c + 1 : 3].fetch(brec + r, c + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                } else {
+                    chs[c].fetch(brec + r, c);
+                }
+                const RecChild<BURST> &ch = chs[c];
                 if (kind == QK_CELL || kind == QK_LEAF) {
                     // A leaf (cumSize 1, com = the point) always interacts, zero if
                     // it is the query's own point (x - y == 0 iff x == y).  A cell is
@@ -1471,7 +1645,7 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(8
                     // Only wm is computed per kind (uniform branch), so the
                     // accumulators stay in place.
                     if (STATS && act) ++nvis;
-                    const double dx = qx - nd.ccx[c], dy = qy - nd.ccy[c];
+                    const double dx = qx - ch.ccx(), dy = qy - ch.ccy();
                     const double D1 = __fma_rn(dx, dx, __fma_rn(dy, dy, 1.0));   // 1 + D, the term's denominator
                     uint64_t takem;
                     double wm;
@@ -1481,23 +1655,24 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(8
                     } else {
                         // the masks straight from the compares (scalar: a
                         // ballot of a combined bool costs two VALU per child)
-                        uint64_t accm = __builtin_amdgcn_ballot_w64(D1 > nd.ca[c]);
-                        const uint64_t band = amask & ~accm & ~__builtin_amdgcn_ballot_w64(D1 < nd.cb[c]);
+                        uint64_t accm = __builtin_amdgcn_ballot_w64(D1 > ch.ca());
+                        const uint64_t band = amask & ~accm & ~__builtin_amdgcn_ballot_w64(D1 < ch.cb());
                         if (band) {   // rare: inside the band the exact IEEE quotient decides
                             bool acc = false;
                             if (__builtin_amdgcn_inverse_ballot_w64(band))
-                                acc = qrec_child_h(nodes, ref, nd.cref[c], virt) /
+                                acc = qrec_child_h(nodes, ref, ch.cref(), virt) /
                                           __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)) < theta;
                             accm |= band & __builtin_amdgcn_ballot_w64(acc);
                         }
                         takem = amask & accm;
-                        wm = (double)(__builtin_amdgcn_inverse_ballot_w64(takem) ? nd.ccnt[c] : 0);
+                        // (BURST: ccnt came with the bundle; a select, no read under the mask)
+                        wm = (double)(__builtin_amdgcn_inverse_ballot_w64(takem) ? ch.ccnt() : 0);
                         const uint64_t om = amask & ~accm;
                         if (om) {
                             if (PART && sp >= STACK) {
                                 if (lane == 0) plim[2] = 1;
                             } else {
-                                if (lane == 0) { L.sref[w][sp] = nd.cref[c]; L.smask[w][sp] = om; }
+                                if (lane == 0) { L.sref[w][sp] = ch.cref(); L.smask[w][sp] = om; }
                                 ++sp;
                             }
                         }
@@ -1520,14 +1695,15 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(8
             if (__builtin_expect((nflags & (0xAA << QNCH_KIND)) != 0, 0)) {
                 for (int c = 0; c < nch; ++c) {
                     const int kind = (nflags >> (QNCH_KIND + 2 * c)) & 3;
+                    const RecChildAt<BURST> rc{brec + r, c};   // (read in place in either order: rare)
                     if (kind == QK_MULTI) {   // a leaf of ccnt copies: 0 if it is the query's point
-                        if (act && !(nd.ccx[c] == qx && nd.ccy[c] == qy)) {
+                        if (act && !(rc.ccx() == qx && rc.ccy() == qy)) {
                             if (STATS) ++nvis;
-                            const double dx = qx - nd.ccx[c], dy = qy - nd.ccy[c];
-                            cell_force(dx, dy, __fma_rn(dx, dx, dy * dy), nd.ccnt[c], fx, fy, zs);
+                            const double dx = qx - rc.ccx(), dy = qy - rc.ccy();
+                            cell_force(dx, dy, __fma_rn(dx, dx, dy * dy), rc.ccnt(), fx, fy, zs);
                         }
                     } else if (kind == QK_TIE) {
-                        const BHNode &tn = nodes[__builtin_amdgcn_readfirstlane(nd.cref[c])];
+                        const BHNode &tn = nodes[__builtin_amdgcn_readfirstlane(rc.cref())];
                         if (STATS) wtie += (unsigned long long)(tn.last - tn.first + 1);
                         for (int p = tn.first; p <= tn.last; ++p) {
                             const double2 pp = pos[p];
@@ -2743,12 +2919,18 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
     // counters only when asked for: visits need every counter, the multi-GPU
     // cost buckets only the waves' run times
     const int mode = visits ? 2 : (bcost ? 1 : 0);
+    // (option trav_burst: the plain and task walks; not the tree partition's)
+    const bool burst = ctx->opts.trav_burst != 0;
     auto kern = plim ? (mode == 2 ? bh_traverse<2, true, false> : mode == 1 ? bh_traverse<1, true, false>
                                                                          : bh_traverse<0, true, false>)
-                     : (mode == 2 ? bh_traverse<2, false, false> : mode == 1 ? bh_traverse<1, false, false>
-                                                                           : bh_traverse<0, false, false>);
-    auto tkern = mode == 2 ? bh_traverse<2, false, true> : mode == 1 ? bh_traverse<1, false, true>
-                                                                     : bh_traverse<0, false, true>;
+                : burst ? (mode == 2 ? bh_traverse<2, false, false, true> : mode == 1 ? bh_traverse<1, false, false, true>
+                                                                                   : bh_traverse<0, false, false, true>)
+                        : (mode == 2 ? bh_traverse<2, false, false> : mode == 1 ? bh_traverse<1, false, false>
+                                                                              : bh_traverse<0, false, false>);
+    auto tkern = burst ? (mode == 2 ? bh_traverse<2, false, true, true> : mode == 1 ? bh_traverse<1, false, true, true>
+                                                                                 : bh_traverse<0, false, true, true>)
+                       : (mode == 2 ? bh_traverse<2, false, true> : mode == 1 ? bh_traverse<1, false, true>
+                                                                           : bh_traverse<0, false, true>);
     const int64_t waves = ceil_div(s1 - s0, 64), nblocks = ceil_div(waves, TRAV_WPB);
     TSNE_REQUIRE(waves <= t.tile_waves, "tile task lists sized for fewer queries");
     // heavy groups: selected after the previous traversal of the same query

@@ -150,6 +150,7 @@ static const OptionField k_options[] = {
     {"tile_stream_frac", &Options::tile_stream_frac, nullptr, 0.0, 64.0},
     {"tile_stream_gate", nullptr, &Options::tile_stream_gate, 0, 1},
     {"trav_prio", nullptr, &Options::trav_prio, 0, 3},
+    {"trav_burst", nullptr, &Options::trav_burst, 0, 1},
     {"trav_front", &Options::trav_front, nullptr, 0.0, 1e6},
     {"trav_front_cur", &Options::trav_front_cur, nullptr, 0.0, 1e6},
     {"wave_log", nullptr, &Options::wave_log, 0, 1},

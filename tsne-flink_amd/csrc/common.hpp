@@ -232,6 +232,8 @@ struct Options {
     double trav_front_cur = 0.0; // > 0: as trav_front, the order predicted from the points' previous costs
                                  // through this build's Morton order (made during the build, second stream)
     int trav_prio = 0;           // 1-3: the 64-query BH traversal's waves at that issue priority (s_setprio)
+    int trav_burst = 1;          // the 64-query BH traversal reads a popped record's fields in bursts (0: one by
+                                 // one, at first use); the same bits either way
     int tile_stream_gate = 1;    // 1: the consumers wait (on the device) until every traversal block has started
     int transform_resort = 10;   // transform steps between Morton sorts of the new points (0: only at setup; no
                                  // result depends on it, transform.hip "Canonical order")
