@@ -283,7 +283,7 @@ def _ceil_div(a, b):
 
 
 def layout3(n, cus):
-    """at_cfg / build_attract_tiles for n rows of a 3-D run on `cus` CUs ->
+    """at_cfg / attract_layout_build for n rows of a 3-D run on `cus` CUs ->
     (configuration, rows per block)."""
     cfg = 4 if _ceil_div(n, 2048) >= cus - cus // 16 else 5
     rbs = min(2048 if cfg == 4 else 512, _ceil_div(_ceil_div(n, cus), 64) * 64)

@@ -3148,4 +3148,42 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
     TSNE_LAUNCH_CHECK();
 }
 
+bool repulsion_stat(tsne_ctx *ctx, const std::string &name, int64_t *value_out) {
+    // indices of bh_traverse's counters (its STATS block): wave pops, tile
+    // points, wave child slots, reference-equivalent evaluations
+    const int at = name == "bh.pops" ? 3 : name == "bh.tile_points" ? 4 : name == "bh.child_slots" ? 6
+                 : name == "bh.visits" ? 0 : name == "bh.wave_ticks_max" ? 15 : name == "bh.wave_ticks_sum" ? 18
+                 : name == "bh.span_ticks" ? 17 : name == "bh.dense_pairs" ? 2 : name == "bh.moment_evals" ? 1
+                 : name == "bh.tile_ticks_max" ? 19 : name == "bh.tile_ticks_sum" ? 22 : name == "bh.tile_span_ticks" ? 21
+                 : name == "bh.slow_wave_ticks" ? 33 : name == "bh.slow_wave_pops" ? 33 : name == "bh.slow_wave_ties" ? 34
+                 : name == "bh.slow_wave_tile_points" ? 35 : name == "bh.slow_wave_slots" ? 36
+                 : name == "bh.wave_mhz" ? 37 : -1;
+    // tile_apply's dense paths k = 0..3 (lane-wise, packed, query-major, staged
+    // sweep): "bh.tile_steps<k>" wave steps issued, "bh.tile_pairs<k>" useful lane pairs
+    int atk = at;
+    if (at < 0 && name.size() == 14 && name.compare(0, 13, "bh.tile_steps") == 0) atk = 24 + 2 * (name[13] - '0');
+    if (at < 0 && name.size() == 14 && name.compare(0, 13, "bh.tile_pairs") == 0) atk = 25 + 2 * (name[13] - '0');
+    // "bh.tile_gsteps<p>_<G>": the wave steps passes over G = 2, 4, 8 consecutive lane-wise windows (p = 0) or
+    // packed rounds (p = 1) would take (counted with tile_pass <= 1); "bh.tile_rounds_max": the most packed
+    // rounds of one wave; "bh.tile_chunked_waves": tile_apply waves that are one chunk of a split list
+    if (at < 0 && name.size() == 17 && name.compare(0, 14, "bh.tile_gsteps") == 0 && name[15] == '_' &&
+        (name[14] == '0' || name[14] == '1') && (name[16] == '2' || name[16] == '4' || name[16] == '8'))
+        atk = (name[14] == '1' ? 38 : 41) + (name[16] == '2' ? 0 : name[16] == '4' ? 1 : 2);
+    if (name == "bh.tile_rounds_max") atk = 44;
+    if (name == "bh.tile_chunked_waves") atk = 45;
+    if (atk < 0 || atk >= VIS_N) return false;
+    TSNE_REQUIRE(ctx->opts.rep_stats && ctx->ws.has("rep.visits"), "counter '" + name + "' needs option rep_stats");
+    unsigned long long v[VIS_N];
+    TSNE_HIP(hipMemcpyAsync(v, ctx->ws.get<unsigned long long>("rep.visits", VIS_N), sizeof(v), hipMemcpyDeviceToHost,
+                            ctx->stream));
+    TSNE_HIP(hipStreamSynchronize(ctx->stream));
+    // span: last wave end - first wave start ([16] holds ~first start), 100 MHz ticks
+    *value_out = atk == 17 ? (int64_t)(v[17] - (~0ull - v[16])) : atk == 21 ? (int64_t)(v[21] - (~0ull - v[20]))
+                                                                              : (int64_t)v[atk];
+    if (atk == 37) *value_out = v[18] ? (int64_t)(100.0 * (double)v[37] / (double)v[18]) : 0;
+    if (atk >= 33 && atk <= 36)   // (ticks << 24 | count) of the slowest wave
+        *value_out = name == "bh.slow_wave_ticks" ? (int64_t)(v[atk] >> 24) : (int64_t)(v[atk] & ((1ull << 24) - 1));
+    return true;
+}
+
 }  // namespace tsne

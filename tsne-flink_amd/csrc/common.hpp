@@ -340,7 +340,7 @@ void opt_destroy(tsne_ctx *ctx);
 int64_t opt_attract_pad(tsne_ctx *ctx);      // stream layout: stored slots per real entry, in parts per million (0: not built)
 int64_t opt_attract_kernel(tsne_ctx *ctx);   // the optimizer's attraction: 0 attract_rows, 1 attract_tiles, 2 attract3,
                                               // 3 attract_tiles3 (-1: none)
-int64_t opt_attract_cfg(tsne_ctx *ctx);      // the tiled layout's configuration (OptState::at_cfg), -1 when it is off
+int64_t opt_attract_cfg(tsne_ctx *ctx);      // the tiled layout's configuration (AttractLayout::at_cfg), -1 when it is off
 BHTree *opt_tree(tsne_ctx *ctx);   // the optimizer's 2-D tree (nullptr without one)
 
 // comm.cpp
