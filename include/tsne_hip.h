@@ -235,7 +235,13 @@ int tsne_ctx_synchronize(tsne_ctx *ctx);
  *                             staged together and walked in one loop; 0: the
  *                             earlier slot-mask loops, a round at a time (the
  *                             same sums, bit for bit, for every value);
- *   "transform_resort" 10     tsne_dev_transform_step: the new points are sorted
+ *   "tile_prefetch" 1         the tile sums' lane-wise windows (tile_pass 0,
+ *                             the traversal waves' own lists, n <= 2^28): 1:
+ *                             a lane gathers the two points of its next step
+ *                             while it sums this step's, through 32-bit offsets
+ *                             from the sorted positions; 0: each step waits
+ *                             for its own gathers (the same sums, bit for bit);
+ *   "transform_resort" 10    tsne_dev_transform_step: the new points are sorted
  *                             again by the map tree's Morton key every this
  *                             many steps (0: only at setup); changes no result,
  *                             only which points share a wave;

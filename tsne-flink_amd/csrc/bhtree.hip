@@ -90,6 +90,18 @@ __device__ __forceinline__ void pair_force_m(bool take, double qx, double qy, do
     fy = __fma_rn(take ? sc : 0.0, dy, fy);
     zs += take ? r : 0.0;
 }
+// pair_force_m with the mask on r alone: without `take` r = 0, so sc = 0 * 0 = 0
+// and every sum takes the same + 0 (the bits of pair_force_m, two selects fewer)
+__device__ __forceinline__ void pair_force_r(bool take, double qx, double qy, double px, double py, double &fx,
+                                             double &fy, double &zs) {
+    const double dx = qx - px, dy = qy - py;
+    const double r0 = recip_bh(__fma_rn(dx, dx, __fma_rn(dy, dy, 1.0)));
+    const double r = take ? r0 : 0.0;
+    const double sc = r * r;
+    fx = __fma_rn(sc, dx, fx);
+    fy = __fma_rn(sc, dy, fy);
+    zs += r;
+}
 
 // omega_i (z) and phi_i (F) weights of S_i = sum D^i, Sx_i = sum D^i w, for
 // A = |v|^2.
@@ -734,6 +746,24 @@ typedef uint64_t u64x2_t __attribute__((ext_vector_type(2)));
 template <class T> __device__ __forceinline__ T lds_fetch(const void *p) {
     typedef const volatile __attribute__((address_space(3))) T *lds_ptr;
     return *(lds_ptr)(const __attribute__((address_space(3))) void *)p;
+}
+// Two points of the sorted positions fetched ahead (option tile_prefetch): the
+// 16 bytes at each of two 32-bit byte offsets from the wave-uniform base (the
+// loads' scalar-base form: no 64-bit address per lane).  The loads are issued
+// where pos_issue2 stands and nothing waits for them there; pos_wait2 on the
+// same pair, with exactly one later pos_issue2 in between, waits until all
+// but that later pair have landed (loads return in order); pos_drain waits
+// for every one.  A pair must not be read, copied or assigned between its
+// issue and its wait: the compiler takes the values for present at the issue.
+__device__ __forceinline__ void pos_issue2(const double2 *base, uint32_t o0, uint32_t o1, f64x2_t &x0, f64x2_t &x1) {
+    asm volatile("global_load_dwordx4 %0, %2, %4\n\tglobal_load_dwordx4 %1, %3, %4"
+                 : "=&v"(x0), "=&v"(x1) : "v"(o0), "v"(o1), "s"(base) : "memory");
+}
+__device__ __forceinline__ void pos_wait2(f64x2_t &x0, f64x2_t &x1) {
+    asm volatile("s_waitcnt vmcnt(2)" : "+v"(x0), "+v"(x1) : : "memory");
+}
+__device__ __forceinline__ void pos_drain(f64x2_t &x0, f64x2_t &x1, f64x2_t &y0, f64x2_t &y1) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(x0), "+v"(x1), "+v"(y0), "+v"(y1) : : "memory");
 }
 template <bool BURST> struct RecHead;
 template <> struct RecHead<false> {
@@ -1952,7 +1982,9 @@ __global__ __launch_bounds__(1024) void narrow_select(int32_t *__restrict__ wcos
 // G x 64 staged points, G x 64 transposed tile masks (the lane-wise windows'
 // tile ranges share their space), G x 64 packed slot ranges, 64 slot marks.
 __host__ __device__ constexpr int tile_lds_wave(int G) { return G * (1024 + 512 + 256) + 256; }
-template <int MODE, int PASS, bool STATS>
+// PF (Options::tile_prefetch; MODE 0, PASS 0 only): the lane-wise windows'
+// steps with the next step's gathers in flight (see "Lane-wise window").
+template <int MODE, int PASS, bool STATS, bool PF = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void tile_apply(
     const double2 *__restrict__ pos, const BHNode *__restrict__ nodes, const TileTask *__restrict__ ttask,
     const int32_t *__restrict__ ttask_n, int64_t g0, int64_t g1, const int32_t *__restrict__ qlist,
@@ -2124,15 +2156,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
             // slot, gathers and refills included), the sweep for the whole window.
             const int cnt_i = b_i - a_i + 1;
             __builtin_amdgcn_wave_barrier();
-            srng[lane] = make_int2(a_i, b_i);
+            srng[lane] = PF ? make_int2(a_i << 4, b_i << 4) : make_int2(a_i, b_i);   // (PF: byte offsets from pos)
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_wave_barrier();
             int cl = 0;
             for (uint64_t wb = W; wb; wb &= wb - 1) {
                 const int2 r = srng[__ffsll((long long)wb) - 1];
-                cl += r.y - r.x + 1;
+                cl += r.y - r.x + (PF ? 16 : 1);
             }
+            if (PF) cl >>= 4;
             const int cmax = wave_max(cl), ctot = wave_sum(lane < wn ? cnt_i : 0);
             if ((float)cmax * LW_COST >= (float)ctot) {
                 masked_until = t + wn;
@@ -2143,6 +2176,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
             // a divergent do-while per lane (two points of one tile per step,
             // the second masked at a tile's odd end): the accumulators are
             // updated in place, not copied at the merges of a wave-uniform loop
+            if constexpr (PF) {
+                // Option tile_prefetch: the same steps, the gathers of a lane's
+                // next step in flight while this step's pairs are summed.  p and
+                // last are byte offsets from pos (32 bits: n <= 2^27, see
+                // tile_apply_launch).  A step's offsets are min(p, last) and
+                // min(p + 16, last): never past the tile's last point (so never
+                // pos[n]), the last point twice at an odd end (masked by `two`)
+                // and for a lane without a next step (never summed).  Every lane
+                // issues both loads in every step (pos_issue2: asm, they stay
+                // where they are issued) and the steps alternate between two
+                // register pairs, so the wait in front of a step's pair terms is
+                // vmcnt(2): on the loads the step before (or the prologue) issued.
+                if (W) {
+                    int i = __ffsll((long long)W) - 1;
+                    W &= W - 1;
+                    int2 r = srng[i];
+                    uint32_t p = (uint32_t)r.x, last = (uint32_t)r.y;
+                    auto gather = [&](f64x2_t &x0, f64x2_t &x1) {
+                        pos_issue2(pos, min(p, last), min(p + 16u, last), x0, x1);
+                    };
+                    auto advance = [&]() -> bool {   // to the lane's next step (false: it has none)
+                        // (the conditions as wave masks: one compare each, combined by scalar
+                        // instructions, and evaluated here, not where the compiler would sink them)
+                        p += 32u;
+                        const uint64_t pm = __ballot(p > last), sm = pm & __ballot(W != 0);
+                        if (__builtin_amdgcn_inverse_ballot_w64(sm)) {
+                            i = __builtin_ctzll(W);   // (W != 0 here)
+                            W &= W - 1;
+                            r = srng[i];
+                            p = (uint32_t)r.x; last = (uint32_t)r.y;
+                        }
+                        return __builtin_amdgcn_inverse_ballot_w64(~pm | sm);
+                    };
+                    f64x2_t a0, a1, b0 = {0.0, 0.0}, b1 = {0.0, 0.0};
+                    gather(a0, a1);
+                    for (;;) {
+                        const uint64_t two_a = __ballot(p < last);   // (before p and last change, in place)
+                        bool more = advance();
+                        gather(b0, b1);
+                        pos_wait2(a0, a1);
+                        __builtin_amdgcn_sched_barrier(0);
+                        pair_force(qx, qy, a0.x, a0.y, ux, uy, uz);
+                        pair_force_r(__builtin_amdgcn_inverse_ballot_w64(two_a), qx, qy, a1.x, a1.y, ux, uy, uz);
+                        if (STATS) { nmine += __builtin_amdgcn_inverse_ballot_w64(two_a) ? 2 : 1; ++nit; }
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (!more) break;
+                        const uint64_t two_b = __ballot(p < last);
+                        more = advance();
+                        gather(a0, a1);
+                        pos_wait2(b0, b1);
+                        __builtin_amdgcn_sched_barrier(0);
+                        pair_force(qx, qy, b0.x, b0.y, ux, uy, uz);
+                        pair_force_r(__builtin_amdgcn_inverse_ballot_w64(two_b), qx, qy, b1.x, b1.y, ux, uy, uz);
+                        if (STATS) { nmine += __builtin_amdgcn_inverse_ballot_w64(two_b) ? 2 : 1; ++nit; }
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (!more) break;
+                    }
+                    pos_drain(a0, a1, b0, b1);   // the pair nobody sums
+                }
+            } else
             if (W) {
                 int i = __ffsll((long long)W) - 1;
                 W &= W - 1;
@@ -2558,12 +2651,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
 // tile_apply<MODE> for Options::tile_pass (0: the slot-bit loops; 1: one round a
 // pass; 2, 4, 8: that many -- the pages and the streaming consumers, whose
 // lists are short, stay at one) and with or without the counters.
+// `prefetch` (Options::tile_prefetch, and the sorted positions within the
+// 32-bit byte offsets of that loop: the caller checks n): the lane-wise
+// windows' prefetching steps, for the slot path's slot-bit kernels (MODE 0,
+// tile_pass 0); the others keep the plain loop.
 template <int MODE, class... Args>
-static void tile_apply_launch(int tile_pass, bool stats, dim3 grid, hipStream_t st, Args... args) {
+static void tile_apply_launch(int tile_pass, bool prefetch, bool stats, dim3 grid, hipStream_t st, Args... args) {
     const int pass = tile_pass == 0 ? 0 : tile_pass == 1 || MODE != 0 ? 1 : 2;
     const int G = pass == 2 ? tile_pass : 1;
     const size_t lds = 4 * (size_t)tile_lds_wave(G);
-#define TSNE_TILE_APPLY(P, S) hipLaunchKernelGGL((tile_apply<MODE, P, S>), grid, dim3(256), lds, st, args..., G)
+#define TSNE_TILE_APPLY(P, S, ...) \
+    hipLaunchKernelGGL((tile_apply<MODE, P, S, ##__VA_ARGS__>), grid, dim3(256), lds, st, args..., G)
+    if constexpr (MODE == 0) {
+        if (pass == 0 && prefetch) {
+            if (stats) TSNE_TILE_APPLY(0, true, true); else TSNE_TILE_APPLY(0, false, true);
+            return;
+        }
+    }
     if (pass == 0) { if (stats) TSNE_TILE_APPLY(0, true); else TSNE_TILE_APPLY(0, false); }
     else if (pass == 1) { if (stats) TSNE_TILE_APPLY(1, true); else TSNE_TILE_APPLY(1, false); }
     else if constexpr (MODE == 0) { if (stats) TSNE_TILE_APPLY(2, true); else TSNE_TILE_APPLY(2, false); }
@@ -3039,7 +3143,7 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
         ChunkView scv;
         scv.Fp = t.st_Dp;
         scv.Zp = t.st_Dz;
-        tile_apply_launch<2>(o.tile_pass, visits != nullptr, dim3(cblocks), ctx->st_stream, t.pos, t.nodes, t.ttask,
+        tile_apply_launch<2>(o.tile_pass, false, visits != nullptr, dim3(cblocks), ctx->st_stream, t.pos, t.nodes, t.ttask,
                              t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.st_mtask, t.st_mtask_n, dF, dz, visits,
                              (const int32_t *)nullptr, scv, t.mom, SpillView(), stv, t.tcost);
         // (F, Z of the traversal itself: read after its launch has ended)
@@ -3089,7 +3193,9 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
     cv.slot_w = t.ch_slot_w; cv.slot_c = t.ch_slot_c; cv.nslots = t.ch_nslots;
     cv.Fp = t.ch_Fp; cv.Zp = t.ch_Zp;
     if (mom_late) TSNE_HIP(hipStreamWaitEvent(st, t.mom_ev, 0));   // t.mom: read from here on
-    tile_apply_launch<0>(o.tile_pass, visits != nullptr, dim3(ceil_div(tslots, 4)), st, t.pos, t.nodes, t.ttask,
+    // (tile_prefetch: its byte offsets from pos, and one step past them, fit 32 bits)
+    const bool tile_pf = o.tile_prefetch != 0 && t.n <= ((int64_t)1 << 27);
+    tile_apply_launch<0>(o.tile_pass, tile_pf, visits != nullptr, dim3(ceil_div(tslots, 4)), st, t.pos, t.nodes, t.ttask,
                          t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.mtask, t.mtask_n, dF, dz, visits, torder, cv,
                          t.mom, SpillView(), stv, t.tcost);
     hipLaunchKernelGGL(moment_apply, dim3(ceil_div(tslots * 64, 256)), dim3(256), 0, st, t.pos, t.nodes, t.mom,
@@ -3105,7 +3211,7 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
                        narrow ? t.nflag : nullptr);
     t.pcost_valid = keep_pcost;
     if (spill) {   // the tasks' tile pages, then their sums into F, Z
-        tile_apply_launch<1>(o.tile_pass, visits != nullptr, dim3(std::max(1, ctx->cu_count * 4)), st, t.pos, t.nodes,
+        tile_apply_launch<1>(o.tile_pass, false, visits != nullptr, dim3(std::max(1, ctx->cu_count * 4)), st, t.pos, t.nodes,
                              t.ttask, t.ttask_n, s0, s1, qlist, t.mom_flag, mom_tol, t.mtask, t.mtask_n, dF, dz, visits,
                              (const int32_t *)nullptr, ChunkView(), t.mom, sv, StreamView(), t.tcost);
         hipLaunchKernelGGL(spill_combine, dim3(ceil_div(s1 - s0, 256)), dim3(256), 0, st, t.sp_gflag, t.sp_gen,

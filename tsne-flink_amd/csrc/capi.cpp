@@ -164,6 +164,7 @@ static const OptionField k_options[] = {
     {"bh_split", nullptr, &Options::bh_split, 0, 1},
     {"build_fuse", nullptr, &Options::build_fuse, 0, 1},
     {"tile_pass", nullptr, &Options::tile_pass, 0, 8},
+    {"tile_prefetch", nullptr, &Options::tile_prefetch, 0, 1},
     {"transform_resort", nullptr, &Options::transform_resort, 0, 1 << 30},
     {"transform_split", nullptr, &Options::transform_split, 0, 1},
     {"transform_stats", nullptr, &Options::transform_stats, 0, 1},

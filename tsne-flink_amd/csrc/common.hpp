@@ -178,6 +178,9 @@ struct Options {
     int tile_pass = 0;        // tile_apply's packed rounds: 0 = slot-bit iteration, one round at a time; 1 = the lane
                               // walks its tiles as runs of slots; 2, 4, 8 = that over passes of so many consecutive
                               // rounds, one convergent walk a pass (the same bits for every value)
+    int tile_prefetch = 1;    // tile_apply's lane-wise windows (tile_pass 0, the slot path): 1 = the next step's two
+                              // points are gathered while this step's are summed, through 32-bit offsets from pos
+                              // (n <= 2^28; the same bits); 0 = each step waits for its own gathers
     int coherent_sort = 1;    // the trees' Morton sort from the previous build's order (csort.hpp; 0: rocPRIM's radix sort)
     double oct_layout_switch = 6.0;   // 3-D: the 8-query layout while the root half-width < this x sqrt(near_dmax)
     int oct_records = 2;      // 3-D: octal records + the 64-query record traversal (1: the 8-query one; 0: the binary-node walk)
