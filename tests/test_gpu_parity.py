@@ -644,7 +644,10 @@ def test_gradient3_outside_root_and_metrics(ctx):
     rp, col, val = random_problem(n, 10, seed=12)
     Y = np.random.default_rng(3).normal(size=(n, 3)) + np.array([4.0, -2.0, 1.0])   # points outside the root
     # (exact duplicates are a documented deviation: the reference restarts their
-    # multiplicity at every split of their leaf, QuadTree.scala:57-60)
+    # multiplicity at every split of their leaf, QuadTree.scala:57-60; the fit's
+    # own rule -- full multiplicity, nothing from a copy at the query's position --
+    # is held against the exact sums and the oracle in test_gpu_octree_edges.py,
+    # with boundary points, key ties, degenerate clouds and small trees)
     for metric in ("sqeuclidean", "euclidean", "cosine"):
         g, Z, _ = ctx.gradient(rp, col, val, Y, 0.5, metric=metric)
         r = O.gradient3(rp, col, val, Y, 0.5, metric=metric)
