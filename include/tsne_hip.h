@@ -337,7 +337,10 @@ int tsne_ctx_loop_profile(tsne_ctx *ctx, char *buf, int64_t cap, int64_t *len_ou
  *                        buffer overflow, a crowd at the k-th distance, or k
  *                        beyond the cross form's buffers), summed over the cross
  *                        form's query slices and a group's ranks.  Kept on the
- *                        host: no synchronisation; no result depends on it. */
+ *                        host: no synchronisation; no result depends on it;
+ *   "quality.fallback_x", "quality.fallback_y"  the same count for the neighbour
+ *                        lists in X and in Y of the handle's last
+ *                        tsne_[dev_]embedding_quality call. */
 int tsne_ctx_counter(tsne_ctx *ctx, const char *name, int64_t *value_out);
 
 /* Diagnostics (option "wave_log" with "rep_stats"): the last counting
@@ -677,6 +680,55 @@ int tsne_init_working_set_pca(tsne_ctx *ctx, const double *X, int64_t n, int32_t
                               double *upd, double *gains);
 int tsne_dev_init_working_set_pca(tsne_ctx *ctx, const double *dX, int64_t n, int32_t d, int32_t c, double *d_Y,
                                   double *d_upd, double *d_gains);
+
+/* ------------------------------------------------------------ scoring a map */
+/* Not in the reference job: the rank-based scores of a map at the map's own
+ * size (no n x n matrix; csrc/ranks.hip).  For a point set A
+ * (n x d, row-major) and a metric:
+ *   D(i, l)      the exact fp64 breeze metric value tsne_knn ranks by and
+ *                returns in dist_out, bit for bit (sequential sums over the
+ *                coordinates, no FMA; cosine: 1 - s / (|a||b|), sequential norms);
+ *   rank_A(i, j) = 1 + #{ l != i : (key(D(i,l)), l) < (key(D(i,j)), j) }, key the
+ *                order-preserving map of a double the kNN sorts by: the 1-based
+ *                position of j in row i of tsne_knn(A, k = n - 1);
+ *   rank_A(i, i) = 0.
+ * Row i is skipped by index, not by distance: duplicates of point i count.
+ * For an input X, a map Y (n x c, ranked by sqeuclidean), k and s scored rows S:
+ *   N_X(i), N_Y(i)  the tsne_knn rows of i in X and in Y (k ids, ascending by (D, j));
+ *   S_T = sum_{i in S} sum_{j in N_Y(i)} max(0, rank_X(i, j) - k);
+ *   S_C = sum_{i in S} sum_{j in N_X(i)} max(0, rank_Y(i, j) - k);
+ *   S_R = sum_{i in S} |N_X(i) & N_Y(i)|                          (all int64);
+ *   trustworthiness = 1 - 2 S_T / (s k (2 n - 3 k - 1)), continuity the same
+ *   with S_C, knn_recall = S_R / (s k).
+ * With S = all rows these are the values of sklearn.manifold.trustworthiness.
+ * Every count is an integer: a result does not depend on the other rows of the
+ * call or on the launch, and repeats bit for bit.
+ * Errors: TSNE_ERR_ARG for a bad metric, an id outside [0, n) (host forms; the
+ * message names the first one; the device forms trust their ids), rows NULL
+ * with s != n, k < 1, 2 n - 3 k - 1 <= 0, s == 0 for the scores;
+ * TSNE_ERR_UNSUPPORTED for m > 1024 and k > 896.  On a tsne_ctx_create_multi
+ * handle these run on the first device. */
+
+/* rank_out[a * m + e] = rank_A(rows[a], cand[a * m + e]) for s rows of m
+ * candidate ids each (m <= 1024; ids may repeat).  rows NULL: row a is point
+ * a, and s must equal n.  s == 0 is a no-op. */
+int tsne_neighbor_ranks(tsne_ctx *ctx, const double *A, int64_t n, int32_t d, int32_t metric, const int64_t *rows,
+                        int64_t s, const int32_t *cand, int32_t m, int32_t *rank_out);
+int tsne_dev_neighbor_ranks(tsne_ctx *ctx, const double *d_A, int64_t n, int32_t d, int32_t metric,
+                            const int64_t *d_rows, int64_t s, const int32_t *d_cand, int32_t m, int32_t *d_rank);
+
+/* scores_out = {trustworthiness, continuity, knn_recall}; sums_out =
+ * {S_T, S_C, S_R} and row_sums_out (s x 3, the same three per scored row) may
+ * be NULL.  rows NULL: every row is scored, and s must equal n.  c >= 1: nothing
+ * is specific to 2 or 3.  The device form takes device pointers for X, Y, the
+ * rows and the row sums, writes scores_out / sums_out on the host and
+ * synchronises the stream. */
+int tsne_embedding_quality(tsne_ctx *ctx, const double *X, int64_t n, int32_t d, int32_t metric, const double *Y,
+                           int32_t c, int32_t k, const int64_t *rows, int64_t s, double scores_out[3],
+                           int64_t sums_out[3], int64_t *row_sums_out);
+int tsne_dev_embedding_quality(tsne_ctx *ctx, const double *d_X, int64_t n, int32_t d, int32_t metric,
+                               const double *d_Y, int32_t c, int32_t k, const int64_t *d_rows, int64_t s,
+                               double scores_out[3], int64_t sums_out[3], int64_t *d_row_sums);
 
 #ifdef __cplusplus
 }

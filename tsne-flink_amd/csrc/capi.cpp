@@ -12,6 +12,7 @@
 #include "bhtree.hpp"
 #include "common.hpp"
 #include "pca.hpp"
+#include "ranks.hpp"
 #include "transform.hpp"
 
 namespace tsne {
@@ -187,6 +188,14 @@ static void set_option(Options &o, const char *key, double v) {
 static double get_option(const Options &o, const char *key) {
     const OptionField &f = option_field(key);
     return f.d ? o.*f.d : (double)(o.*f.i);
+}
+
+// the host forms' ids: every one in [0, n), the first bad one named
+template <class T> static void check_ids(const char *what, const T *ids, int64_t count, int64_t n) {
+    for (int64_t e = 0; e < count; ++e)
+        if (ids[e] < 0 || (int64_t)ids[e] >= n)
+            fail(TSNE_ERR_ARG, std::string(what) + "[" + std::to_string(e) + "] = " + std::to_string((long long)ids[e]) +
+                                   " out of [0, n)");
 }
 
 }  // namespace tsne
@@ -469,6 +478,8 @@ int tsne_ctx_counter(tsne_ctx *ctx, const char *name, int64_t *value_out) {
             *value_out = opt_tree(ctx) ? bh_stream_counter(ctx, *opt_tree(ctx)) : 0;
         else if (k.rfind("bh.", 0) == 0 && repulsion_stat(ctx, k, value_out)) {}
         else if (k == "xform3.pops") *value_out = transform_pops(ctx);
+        else if (k == "quality.fallback_x") *value_out = ctx->quality_fallbacks[0];
+        else if (k == "quality.fallback_y") *value_out = ctx->quality_fallbacks[1];
         else if (k == "comm.kind") *value_out = comm_counter(ctx, false);
         else if (k == "comm.calls") *value_out = comm_counter(ctx, true);
         else if (k == "opt.csort_oversized") *value_out = opt_tree(ctx) ? csort_oversized(ctx, opt_tree(ctx)->cs) : 0;
@@ -1312,6 +1323,108 @@ int tsne_dev_init_working_set_pca(tsne_ctx *ctx, const double *dX, int64_t n, in
         ctx = primary(ctx);
         DeviceGuard g(ctx->device);
         pca_init_device(ctx, dX, n, d, c, d_Y, d_upd, d_gains);
+    });
+}
+
+// ------------------------------------------------ scoring a map (ranks.hpp)
+
+static void check_rank_args(int64_t n, int32_t d, int32_t metric, const void *rows, int64_t s) {
+    TSNE_REQUIRE(n >= 1 && d >= 1, "bad sizes");
+    TSNE_REQUIRE(metric >= 0 && metric <= 2, "unknown metric");
+    TSNE_REQUIRE(s >= 0, "bad number of rows");
+    TSNE_REQUIRE(rows != nullptr || s == n, "rows is NULL (all rows): s must equal n");
+}
+
+int tsne_neighbor_ranks(tsne_ctx *ctx, const double *A, int64_t n, int32_t d, int32_t metric, const int64_t *rows,
+                        int64_t s, const int32_t *cand, int32_t m, int32_t *rank_out) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        if (s == 0) return;
+        check_rank_args(n, d, metric, rows, s);
+        TSNE_REQUIRE(m >= 1, "m must be positive");
+        TSNE_REQUIRE(A && cand && rank_out, "NULL buffer");
+        if (rows) check_ids("rows", rows, s, n);
+        check_ids("cand", cand, s * (int64_t)m, n);
+        double *dA = upload(ctx, "h.X", A, (size_t)n * (size_t)d);
+        int64_t *dr = rows ? upload(ctx, "h.qrows", rows, (size_t)s) : nullptr;
+        int32_t *dc = upload(ctx, "h.cand", cand, (size_t)s * (size_t)m);
+        int32_t *dk = ctx->ws.get<int32_t>("h.rank", (size_t)s * (size_t)m);
+        ranks_device(ctx, dA, n, d, metric, dr, s, dc, m, dk);
+        download(ctx, rank_out, dk, (size_t)s * (size_t)m);
+        sync(ctx);
+    });
+}
+
+int tsne_dev_neighbor_ranks(tsne_ctx *ctx, const double *d_A, int64_t n, int32_t d, int32_t metric,
+                            const int64_t *d_rows, int64_t s, const int32_t *d_cand, int32_t m, int32_t *d_rank) {
+    return guard([&] {
+        check_ctx(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        if (s == 0) return;
+        check_rank_args(n, d, metric, d_rows, s);
+        ranks_device(ctx, d_A, n, d, metric, d_rows, s, d_cand, m, d_rank);
+    });
+}
+
+static void quality_scores(const int64_t sums[3], int64_t n, int32_t k, int64_t s, double scores_out[3],
+                           int64_t *sums_out) {
+    scores_out[0] = quality_trust(sums[0], n, k, s);
+    scores_out[1] = quality_trust(sums[1], n, k, s);
+    scores_out[2] = quality_recall(sums[2], k, s);
+    if (sums_out) std::copy(sums, sums + 3, sums_out);
+}
+
+static void check_quality_args(int64_t n, int32_t d, int32_t metric, int32_t c, int32_t k, const void *rows,
+                               int64_t s) {
+    TSNE_REQUIRE(n >= 2 && d >= 1 && c >= 1, "bad sizes");
+    TSNE_REQUIRE(metric >= 0 && metric <= 2, "unknown metric");
+    TSNE_REQUIRE(k >= 1, "k must be positive");
+    TSNE_REQUIRE(2 * n - 3 * (int64_t)k - 1 > 0, "the scores need 2 n - 3 k - 1 > 0");
+    TSNE_REQUIRE(s >= 1, "no rows to score");
+    TSNE_REQUIRE(rows != nullptr || s == n, "rows is NULL (all rows): s must equal n");
+}
+
+int tsne_embedding_quality(tsne_ctx *ctx, const double *X, int64_t n, int32_t d, int32_t metric, const double *Y,
+                           int32_t c, int32_t k, const int64_t *rows, int64_t s, double scores_out[3],
+                           int64_t sums_out[3], int64_t *row_sums_out) {
+    return guard([&] {
+        check_ctx(ctx);
+        knn_counter_reset(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        check_quality_args(n, d, metric, c, k, rows, s);
+        TSNE_REQUIRE(X && Y && scores_out, "NULL buffer");
+        if (rows) check_ids("rows", rows, s, n);
+        double *dX = upload(ctx, "h.X", X, (size_t)n * (size_t)d);
+        double *dY = upload(ctx, "h.Y", Y, (size_t)n * (size_t)c);
+        int64_t *dr = rows ? upload(ctx, "h.qrows", rows, (size_t)s) : nullptr;
+        int64_t *drs = row_sums_out ? ctx->ws.get<int64_t>("h.row_sums", (size_t)s * 3) : nullptr;
+        int64_t sums[3];
+        quality_device(ctx, dX, n, d, metric, dY, c, k, dr, s, drs, sums);
+        if (row_sums_out) {
+            download(ctx, row_sums_out, drs, (size_t)s * 3);
+            sync(ctx);
+        }
+        quality_scores(sums, n, k, s, scores_out, sums_out);
+    });
+}
+
+int tsne_dev_embedding_quality(tsne_ctx *ctx, const double *d_X, int64_t n, int32_t d, int32_t metric,
+                               const double *d_Y, int32_t c, int32_t k, const int64_t *d_rows, int64_t s,
+                               double scores_out[3], int64_t sums_out[3], int64_t *d_row_sums) {
+    return guard([&] {
+        check_ctx(ctx);
+        knn_counter_reset(ctx);
+        ctx = primary(ctx);
+        DeviceGuard g(ctx->device);
+        check_quality_args(n, d, metric, c, k, d_rows, s);
+        TSNE_REQUIRE(d_X && d_Y && scores_out, "NULL buffer");
+        int64_t sums[3];
+        quality_device(ctx, d_X, n, d, metric, d_Y, c, k, d_rows, s, d_row_sums, sums);
+        quality_scores(sums, n, k, s, scores_out, sums_out);
     });
 }
 

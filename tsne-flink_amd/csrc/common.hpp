@@ -272,6 +272,7 @@ struct tsne_ctx {
     int32_t *pinned = nullptr;   // small pinned host scratch (per-iteration read-backs)
     int cu_count = 256;
     int64_t knn_fallback_queries = 0;   // queries of the last kNN call answered by the exact scan ("knn.fallback_queries")
+    int64_t quality_fallbacks[2] = {0, 0};   // the same of the last score's neighbour lists in X and in Y ("quality.fallback_x/_y")
     // tsne_ctx_create_multi: the per-device contexts (ranks) of a group
     // handle; host-buffer operators fan out over them, one thread per rank
     std::vector<tsne_ctx *> group;

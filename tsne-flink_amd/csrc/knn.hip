@@ -29,6 +29,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.hpp"
+#include "metric.hpp"
 
 namespace tsne {
 namespace {
@@ -91,9 +92,7 @@ __global__ void prep_rows(const double *__restrict__ X, int64_t n, int32_t d, in
     double scale = 1.0;
     if (metric == TSNE_METRIC_COSINE) {
         if (lane == 0) {  // exact sequential norm, as breeze norm()
-            double s = 0.0;
-            for (int c = 0; c < d; ++c) s = __dadd_rn(s, __dmul_rn(x[c], x[c]));
-            norm64[row] = sqrt(s);
+            norm64[row] = exact_norm(x, d);
         }
         double s = 0.0;
         for (int c = lane; c < d; c += 64) s += x[c] * x[c];
@@ -582,22 +581,7 @@ __global__ __launch_bounds__(256) void knn_compact(
 }
 
 // -------------------------------------------------------------- rerank
-// Exact breeze metric in fp64, sequential over the coordinates (no FMA).
-__device__ __forceinline__ double exact_metric(const double *__restrict__ a,
-                                               const double *__restrict__ b, int32_t d,
-                                               int32_t metric, double na, double nb) {
-    if (metric == TSNE_METRIC_COSINE) {
-        double s = 0.0;
-        for (int32_t t = 0; t < d; ++t) s = __dadd_rn(s, __dmul_rn(a[t], b[t]));
-        return 1.0 - s / (na * nb);
-    }
-    double s = 0.0;
-    for (int32_t t = 0; t < d; ++t) {
-        double df = __dsub_rn(a[t], b[t]);
-        s = __dadd_rn(s, __dmul_rn(df, df));
-    }
-    return metric == TSNE_METRIC_EUCLIDEAN ? sqrt(s) : s;
-}
+// The exact breeze metric in fp64 is exact_metric (metric.hpp, shared with ranks.hip).
 
 // One wave per query (WG of 64 threads), bitonic sort of (key(d), j) in LDS.
 template <int CAP>

@@ -38,7 +38,7 @@ double now() {
 
 DeviceRun runOnDevice(tsne_ctx *ctx, const std::vector<double> &X, int64_t n, int32_t d, int32_t k,
                       double perplexity, const tsne_params &p, int64_t randomState, bool initPca,
-                      int32_t pcaDimension) {
+                      int32_t pcaDimension, int32_t qualityK, const std::vector<int64_t> *qualityRows) {
     if (n < 2) throw std::invalid_argument("the device pipeline needs at least two points");
     DeviceRun out;
     const int64_t kk = std::min<int64_t>(k, n - 1);
@@ -49,8 +49,9 @@ DeviceRun runOnDevice(tsne_ctx *ctx, const std::vector<double> &X, int64_t n, in
     DevArray<int32_t> idx((size_t)(n * kk));
     DevArray<double> dist((size_t)(n * kk));
     DevArray<double> dY(ne), dU(ne), dG(ne);
+    // the input rows: freed after the kNN, or kept for the scores when qualityK > 0
+    DevArray<double> dX((size_t)n * d);
     {
-        DevArray<double> dX((size_t)n * d);
         hipCheck(hipMemcpy(dX.p, X.data(), sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice), "H2D X");
         if (pcaDimension > 0) {
             // the scores of the leading components in a second buffer; the kNN reads them
@@ -58,7 +59,7 @@ DeviceRun runOnDevice(tsne_ctx *ctx, const std::vector<double> &X, int64_t n, in
             DevArray<double> dS((size_t)n * cOut), dE((size_t)cOut);
             libCheck(tsne_dev_pca(ctx, dX.p, n, d, cOut, nullptr, nullptr, dE.p, dS.p));
             libCheck(tsne_ctx_synchronize(ctx));
-            dX.release();
+            if (qualityK <= 0) dX.release();
             if (initPca) {   // Y = scores[:, :C] * (1e-4 / sqrt(lambda_1)), as tsne_init_working_set_pca
                 double lambda1 = 0.0;
                 hipCheck(hipMemcpy(&lambda1, dE.p, sizeof(double), hipMemcpyDeviceToHost), "D2H lambda_1");
@@ -91,6 +92,7 @@ DeviceRun runOnDevice(tsne_ctx *ctx, const std::vector<double> &X, int64_t n, in
             libCheck(tsne_ctx_synchronize(ctx));
         }
     }
+    if (qualityK <= 0) dX.release();
     out.t_knn = now() - t0;
     t0 = now();
     // pairwiseAffinities (:162-180) over the kNN rows, jointDistribution (:182-196)
@@ -135,6 +137,19 @@ DeviceRun runOnDevice(tsne_ctx *ctx, const std::vector<double> &X, int64_t n, in
     libCheck(tsne_dev_opt_losses(ctx, keys.data(), vals.data(), lcap, &nl));
     for (int32_t i = 0; i < std::min(nl, lcap); ++i) out.loss[keys[(size_t)i]] += vals[(size_t)i];
     out.t_loop = now() - t0;
+    if (qualityK > 0) {   // the scores of the map on the input rows as read, both still in HBM
+        t0 = now();
+        const bool all = !qualityRows || qualityRows->empty();
+        const int64_t s = all ? n : (int64_t)qualityRows->size();
+        DevArray<int64_t> rows(all ? 0 : (size_t)s);
+        if (!all)
+            hipCheck(hipMemcpy(rows.p, qualityRows->data(), sizeof(int64_t) * (size_t)s, hipMemcpyHostToDevice), "H2D rows");
+        const int rc = tsne_dev_embedding_quality(ctx, dX.p, n, d, p.metric, dY.p, C, qualityK, all ? nullptr : rows.p, s,
+                                                  out.quality, nullptr, nullptr);
+        if (rc == TSNE_ERR_ARG) throw std::invalid_argument(tsne_last_error());
+        libCheck(rc);
+        out.t_quality = now() - t0;
+    }
     return out;
 }
 

@@ -21,6 +21,8 @@ struct DeviceRun {
     int64_t nnz = 0;                   // entries of the joint distribution P
     double t_knn = 0, t_aff = 0, t_loop = 0;   // seconds, each stage to its completion
     double t_pca = 0;                  // the PCA in front of the kNN and / or of the working set (part of t_knn)
+    double quality[3] = {0, 0, 0};     // qualityK > 0: trustworthiness, continuity, kNN recall of the map
+    double t_quality = 0;
 };
 
 // X: n x d row-major (rows = the sorted ids).  Exact kNN (k neighbours, as
@@ -33,8 +35,13 @@ struct DeviceRun {
 // initWorkingSet(randomState) -- with pcaDimension > 0 from the same scores
 // (one PCA of max(pcaDimension, n_components) components), else
 // tsne_dev_init_working_set_pca.
+// qualityK > 0: X stays in HBM beside the chain, and after the last iteration
+// the map is scored against it over qualityK neighbours
+// (tsne_dev_embedding_quality: the rows as read and p.metric, also under
+// pcaDimension) on the rows *qualityRows (NULL or empty: every row).
 DeviceRun runOnDevice(tsne_ctx *ctx, const std::vector<double> &X, int64_t n, int32_t d, int32_t k,
                       double perplexity, const tsne_params &p, int64_t randomState, bool initPca = false,
-                      int32_t pcaDimension = 0);
+                      int32_t pcaDimension = 0, int32_t qualityK = 0,
+                      const std::vector<int64_t> *qualityRows = nullptr);
 
 }  // namespace tsne_flink

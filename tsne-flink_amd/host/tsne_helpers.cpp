@@ -239,6 +239,35 @@ PcaScores TsneHelpers::pca(const std::vector<double> &X, int64_t n, int32_t d, i
     return r;
 }
 
+QualityScores TsneHelpers::embeddingQuality(const std::vector<double> &X, int64_t n, int32_t d, int32_t metric,
+                                            const std::vector<double> &y, int32_t c, int32_t k,
+                                            const std::vector<int64_t> &rows) {
+    double sc[3] = {0, 0, 0};
+    check(tsne_embedding_quality(ctx_, X.data(), n, d, metric, y.data(), c, k, rows.empty() ? nullptr : rows.data(),
+                                 rows.empty() ? n : (int64_t)rows.size(), sc, nullptr, nullptr));
+    return {sc[0], sc[1], sc[2]};
+}
+
+std::vector<int64_t> qualityRows(int64_t n, int64_t sample) {
+    std::vector<int64_t> rows;
+    if (sample <= 0 || sample >= n) return rows;
+    rows.resize((size_t)sample);
+    for (int64_t a = 0; a < sample; ++a) rows[(size_t)a] = a * n / sample;
+    return rows;
+}
+
+void checkQualityK(int64_t n, long k) {
+    if (k < 1) throw std::invalid_argument("--quality needs K >= 1");
+    if (2 * n - 3 * (int64_t)k - 1 <= 0)
+        throw std::invalid_argument("--quality " + std::to_string(k) + ": the scores need 2 n - 3 K - 1 > 0 (n = " +
+                                    std::to_string(n) + ")");
+}
+
+std::string qualityFileText(const QualityScores &q) {
+    return "trustworthiness=" + javaDouble(q.trustworthiness) + "\ncontinuity=" + javaDouble(q.continuity) +
+           "\nknnRecall=" + javaDouble(q.knnRecall) + "\n";
+}
+
 double pcaInitScale(double lambda1) {
     if (!(lambda1 > 0.0)) throw std::invalid_argument("PCA initialisation of constant data (lambda_1 <= 0)");
     return 1e-4 / std::sqrt(lambda1);

@@ -66,6 +66,19 @@ std::vector<double> leadingColumns(const std::vector<double> &rows, int64_t n, i
 // tsne_init_working_set_pca on the same rows (a score does not depend on c_out).
 WorkingSet workingSetFromScores(const std::vector<int32_t> &ids, const PcaScores &pca, int32_t nComponents);
 
+// --quality: the rank-based scores of the fitted map (tsne_embedding_quality;
+// not in the reference job).
+struct QualityScores {
+    double trustworthiness = 0, continuity = 0, knnRecall = 0;
+};
+// The scored rows of --qualitySample S: S == 0 or S >= n scores every row
+// (empty result), else the strided sample i_a = (a * n) / S, a < S.
+std::vector<int64_t> qualityRows(int64_t n, int64_t sample);
+// --quality K is refused (std::invalid_argument) unless K >= 1 and 2 n - 3 K - 1 > 0.
+void checkQualityK(int64_t n, long k);
+// The three lines of --qualityFile, each value as java.lang.Double.toString.
+std::string qualityFileText(const QualityScores &q);
+
 class TsneHelpers {
   public:
     explicit TsneHelpers(int device = 0);
@@ -92,6 +105,11 @@ class TsneHelpers {
                                  int32_t nComponents);
     // --pcaDimension: eigenvalues and scores of the leading c_out components of X (n x d)
     PcaScores pca(const std::vector<double> &X, int64_t n, int32_t d, int32_t c_out);
+    // --quality on the host chain: the scores of the map y (n x c) of the rows X
+    // (n x d) over k neighbours on the rows `rows` (empty: every row)
+    QualityScores embeddingQuality(const std::vector<double> &X, int64_t n, int32_t d, int32_t metric,
+                                   const std::vector<double> &y, int32_t c, int32_t k,
+                                   const std::vector<int64_t> &rows);
     // TsneHelpers.scala:221-318 (one evaluation; exaggeration multiplies P)
     std::vector<std::pair<int32_t, std::vector<double>>> gradient(const std::vector<Triple> &P,
                                                                   const WorkingSet &embedding,

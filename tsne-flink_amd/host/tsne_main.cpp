@@ -9,6 +9,7 @@
 //            [--finalMomentum 0.8] [--theta 0.25] [--loss loss.txt | --lossFile loss.txt]
 //            [--knnIterations 3] [--knnBlocks P] [--inputDistanceMatrix] [--executionPlan]
 //            [--device 0] [--hostChain] [--init random|pca] [--pcaDimension 0]
+//            [--quality 0] [--qualitySample 10000] [--qualityFile quality.txt]
 // Beyond the reference's flags: --init pca starts from the PCA initialisation
 // of the input rows (tsne_init_working_set_pca; --randomState is then unused)
 // instead of the seeded N(0, 1e-4^2); --pcaDimension p > 0 runs the kNN on the
@@ -19,6 +20,12 @@
 // --pcaDimension with --knnMethod project (its Z-order comparator is a total
 // order only for nonnegative inputs; scores are signed), either flag with
 // --inputDistanceMatrix (no rows), p > min(dimension, 64).
+// --quality K > 0 scores the fitted map against the input rows as read (with
+// --metric; under --pcaDimension too the original rows, not the PCA scores)
+// over K neighbours: trustworthiness, continuity and kNN recall
+// (tsne_embedding_quality) on --qualitySample rows (strided, i_a = a n / S; 0 or
+// >= n: every row), written to --qualityFile as three name=value lines.
+// Refused: --quality with --inputDistanceMatrix, K < 1, 2 n - 3 K - 1 <= 0.
 // The exact kNN methods run kNN -> affinities -> joint -> optimize resident
 // in HBM (device_pipeline.hpp); --hostChain (and --knnMethod project, the
 // distance-matrix input) take the TsneHelpers mirror, whose operators pass
@@ -129,6 +136,16 @@ int main(int argc, char **argv) {
             throw std::invalid_argument("pcaDimension exceeds min(dimension, 64)");
         if (initPca && nComponents > inputDimension)
             throw std::invalid_argument("--init pca: nComponents exceeds the input's dimension");
+        const bool quality = parameters.has("quality");
+        if (quality && parameters.get("quality", "") == "__NO_VALUE_KEY")
+            throw std::invalid_argument("--quality needs K >= 1");
+        const long qualityK = parameters.getLong("quality", 0);
+        const long qualitySample = parameters.getLong("qualitySample", 10000);
+        const std::string qualityFile = parameters.get("qualityFile", "quality.txt");
+        if (quality && inputDistanceMatrix)
+            throw std::invalid_argument("--quality needs the input rows, not a distance matrix");
+        if (quality && qualityK < 1) throw std::invalid_argument("--quality needs K >= 1");
+        if (quality && qualitySample < 0) throw std::invalid_argument("qualitySample must not be negative");
 
         if (getExecutionPlan) {  // Tsne.scala:89-95: write the plan instead of executing
             std::ofstream pw("tsne_executionPlan.json");
@@ -161,6 +178,8 @@ int main(int argc, char **argv) {
         bool done = false;
         std::vector<double> X;     // the input rows (kept for the host chain's --init pca)
         PcaScores pcaScores;       // --pcaDimension on the host chain
+        QualityScores scores;      // --quality
+        double tQuality = 0.0;
         if (inputDistanceMatrix) {
             knn = toCsr(readDistanceMatrix(inputPath));
         } else {
@@ -171,11 +190,19 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "[tsne_hip] read %zu points in %.3f s\n", ids.size(), t1 - t0);
             if (knnMethod != "bruteforce" && knnMethod != "partition" && knnMethod != "project")
                 throw std::invalid_argument("Knn method '" + metricName + "' not defined");  // Tsne.scala:78
+            if (quality) checkQualityK((int64_t)ids.size(), qualityK);   // before any device work
+            const std::vector<int64_t> qrows = quality ? qualityRows((int64_t)ids.size(), qualitySample)
+                                                       : std::vector<int64_t>();
             if (knnMethod != "project" && ids.size() >= 2 && !parameters.has("hostChain")) {
                 // the exact kNN methods: the whole chain resident in HBM (device_pipeline.hpp);
                 // --hostChain runs the TsneHelpers mirror's host round trips instead
                 DeviceRun run = runOnDevice(h.context(), X, (int64_t)ids.size(), inputDimension, (int32_t)neighbors,
-                                            perplexity, prm, randomState, initPca, (int32_t)pcaDimension);
+                                            perplexity, prm, randomState, initPca, (int32_t)pcaDimension,
+                                            quality ? (int32_t)qualityK : 0, &qrows);
+                if (quality) {
+                    scores = {run.quality[0], run.quality[1], run.quality[2]};
+                    tQuality = run.t_quality;
+                }
                 if (initPca || pcaDimension > 0) std::fprintf(stderr, "[tsne_hip] PCA in %.3f s\n", run.t_pca);
                 std::fprintf(stderr, "[tsne_hip] kNN in %.3f s\n", run.t_knn);
                 std::fprintf(stderr, "[tsne_hip] affinities + joint in %.3f s (nnz %lld)\n", run.t_aff,
@@ -201,7 +228,8 @@ int main(int argc, char **argv) {
                                              (int32_t)knnIterations, randomState);
                 std::fprintf(stderr, "[tsne_hip] kNN in %.3f s\n", now() - t1);
             }
-            if (done || !initPca || pcaDimension > 0) std::vector<double>().swap(X);   // only the host chain's PCA start reads the rows again
+            // only the host chain's PCA start and its --quality read the rows again
+            if (done || (!quality && (!initPca || pcaDimension > 0))) std::vector<double>().swap(X);
         }
         if (!done) {
             double t2 = now();
@@ -232,6 +260,21 @@ int main(int argc, char **argv) {
             h.optimizeCsr(P, ws, learningRate, (int32_t)iterations, metric, earlyExaggeration, initialMomentum,
                           finalMomentum, theta, &loss);
             std::fprintf(stderr, "[tsne_hip] %ld iterations in %.3f s\n", iterations, now() - t3);
+            if (quality) {
+                // the map's rows are the input's rows (every point has a neighbour), row for row
+                if (ws.ids.size() * (size_t)inputDimension != X.size())
+                    throw std::invalid_argument("--quality: a point of the input has no row in the map");
+                double t4 = now();
+                scores = h.embeddingQuality(X, (int64_t)ws.ids.size(), inputDimension, metric, ws.y,
+                                            (int32_t)nComponents, (int32_t)qualityK,
+                                            qualityRows((int64_t)ws.ids.size(), qualitySample));
+                tQuality = now() - t4;
+            }
+        }
+        if (quality) {
+            std::fprintf(stderr, "[tsne_hip] quality in %.3f s\n", tQuality);
+            std::ofstream qf(qualityFile);
+            qf << qualityFileText(scores);
         }
 
         {   // result.map(x => (x._1, x._2(0), x._2(1))).writeAsCsv (Tsne.scala:86);

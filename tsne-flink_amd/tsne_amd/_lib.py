@@ -108,6 +108,10 @@ SIGNATURES = {
     "tsne_dev_pca": (C.c_int, [P, P, I64, I32, I32, P, P, P, P]),
     "tsne_init_working_set_pca": (C.c_int, [P, P, I64, I32, I32, P, P, P]),
     "tsne_dev_init_working_set_pca": (C.c_int, [P, P, I64, I32, I32, P, P, P]),
+    "tsne_neighbor_ranks": (C.c_int, [P, P, I64, I32, I32, P, I64, P, I32, P]),
+    "tsne_dev_neighbor_ranks": (C.c_int, [P, P, I64, I32, I32, P, I64, P, I32, P]),
+    "tsne_embedding_quality": (C.c_int, [P, P, I64, I32, I32, P, I32, I32, P, I64, P, P, P]),
+    "tsne_dev_embedding_quality": (C.c_int, [P, P, I64, I32, I32, P, I32, I32, P, I64, P, P, P]),
 }
 
 _lib = None

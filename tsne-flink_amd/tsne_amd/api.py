@@ -3,11 +3,12 @@
 Arguments are numpy arrays (host) or torch CUDA tensors (device API).  Names
 and argument meaning follow the reference's Scala methods.
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
-from ._lib import METRICS, UNIQUE_ID_BYTES, CommOps, Params, check, lib
+from ._lib import METRICS, UNIQUE_ID_BYTES, CommOps, Params, check, lib, metric_from_name
 
 
 def _ptr(a):
@@ -49,6 +50,31 @@ def _map_dim(Y):
     if Y.ndim != 2 or Y.shape[1] not in (2, 3):
         raise ValueError("the map must be n x 2 or n x 3, got shape %s" % (tuple(Y.shape),))
     return int(Y.shape[1])
+
+
+Quality = collections.namedtuple("Quality", "trustworthiness continuity knn_recall sums row_sums")
+
+
+def quality_rows(n, s):
+    """The strided sample of s of n rows, i_a = (a * n) // s: no generator, so the
+    same call scores the same rows (the CLI's --qualitySample uses the same rule)."""
+    return (np.arange(int(s), dtype=np.int64) * int(n)) // max(int(s), 1)
+
+
+def _rows(n, rows):
+    """None (every row), an int (quality_rows) or an array of ids -> None or int64 array."""
+    if rows is None:
+        return None
+    if isinstance(rows, (int, np.integer)):
+        return quality_rows(n, rows)
+    return np.ascontiguousarray(rows, dtype=np.int64).ravel()
+
+
+def _metric_id(metric):
+    """A metric name or id -> the id; an unknown name raises the library's TSNE_ERR_ARG."""
+    if isinstance(metric, str):
+        return METRICS[metric] if metric in METRICS else metric_from_name(metric)
+    return int(metric)
 
 
 def default_params(**kw):
@@ -357,6 +383,62 @@ class Context:
         n, d = dX.shape
         check(lib().tsne_dev_init_working_set_pca(self._h, _ptr(dX), n, d, dY.shape[1], _ptr(dY), _ptr(dupd),
                                                   _ptr(dgains)))
+
+    # ---- scoring a map (include/tsne_hip.h "scoring a map")
+    def neighborRanks(self, A, cand, rows=None, metric="sqeuclidean"):
+        """tsne_neighbor_ranks -> rank[s, m] int32: the exact rank of cand[a, e] among
+        all points as seen from row rows[a] of A (0 for the row itself; 1-based
+        position in tsne_knn(A, n - 1) otherwise).  rows: None (every row), an int
+        s (quality_rows(n, s)) or an array of point ids."""
+        A = _f64(A)
+        n, d = A.shape
+        rows = _rows(n, rows)
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+        s = n if rows is None else len(rows)
+        if cand.ndim != 2 or cand.shape[0] != s:
+            raise ValueError("cand has shape %s, expected (%d, m)" % (cand.shape, s))
+        rank = np.zeros(cand.shape, dtype=np.int32)
+        check(lib().tsne_neighbor_ranks(self._h, _ptr(A), n, d, _metric_id(metric), _ptr(rows), s, _ptr(cand),
+                                        cand.shape[1], _ptr(rank)))
+        return rank
+
+    def embeddingQuality(self, X, Y, k, metric="sqeuclidean", rows=None):
+        """tsne_embedding_quality -> Quality(trustworthiness, continuity, knn_recall,
+        sums[3] int64 = (S_T, S_C, S_R), row_sums[s, 3] int64) of the map Y of the
+        input X over k neighbours.  rows as for neighborRanks."""
+        X, Y = _f64(X), _f64(Y)
+        n, d = X.shape
+        if Y.ndim != 2 or Y.shape[0] != n:
+            raise ValueError("Y has shape %s, expected (%d, c)" % (Y.shape, n))
+        rows = _rows(n, rows)
+        s = n if rows is None else len(rows)
+        scores = np.zeros(3)
+        sums = np.zeros(3, dtype=np.int64)
+        row_sums = np.zeros((s, 3), dtype=np.int64)
+        check(lib().tsne_embedding_quality(self._h, _ptr(X), n, d, _metric_id(metric), _ptr(Y), Y.shape[1], k,
+                                           _ptr(rows), s, _ptr(scores), _ptr(sums), _ptr(row_sums)))
+        return Quality(float(scores[0]), float(scores[1]), float(scores[2]), sums, row_sums)
+
+    def dev_neighbor_ranks(self, dA, d_cand, d_rank, d_rows=None, metric="sqeuclidean"):
+        """tsne_dev_neighbor_ranks on torch tensors (d_cand / d_rank int32 s x m,
+        d_rows int64 or None = every row); ready after synchronize()."""
+        self._fence(dA)
+        n, d = dA.shape
+        s, m = d_cand.shape
+        check(lib().tsne_dev_neighbor_ranks(self._h, _ptr(dA), n, d, _metric_id(metric), _ptr(d_rows), s, _ptr(d_cand),
+                                            m, _ptr(d_rank)))
+
+    def dev_embedding_quality(self, dX, dY, k, metric="sqeuclidean", d_rows=None, d_row_sums=None):
+        """tsne_dev_embedding_quality on torch tensors -> Quality (row_sums is
+        d_row_sums, int64 s x 3 on the device, or None); synchronises."""
+        self._fence(dX)
+        n, d = dX.shape
+        s = n if d_rows is None else d_rows.shape[0]
+        scores = np.zeros(3)
+        sums = np.zeros(3, dtype=np.int64)
+        check(lib().tsne_dev_embedding_quality(self._h, _ptr(dX), n, d, _metric_id(metric), _ptr(dY), dY.shape[1], k,
+                                               _ptr(d_rows), s, _ptr(scores), _ptr(sums), _ptr(d_row_sums)))
+        return Quality(float(scores[0]), float(scores[1]), float(scores[2]), sums, d_row_sums)
 
     def optimize(self, row_ptr, col, P, Y, upd, gains, params):
         """TsneHelpers.scala:396-430, in place; returns {iteration: loss}."""
