@@ -228,7 +228,17 @@ int tsne_ctx_synchronize(tsne_ctx *ctx);
  *                             the subtree moments run on the second stream
  *                             beside the traversal; 0: one launch per pass
  *                             (the same arrays, bit for bit);
- *   "tile_pass" 0             the tile sums' packed rounds (<= 64 points of
+ *   "bh_chain" 1              2-D Barnes-Hut, where the tile sums wait for
+ *                             nothing they do not read: the subtree moments
+ *                             "build_fuse" defers run on a stream of their own
+ *                             from the traversal's start, the narrow groups'
+ *                             moment sums and the next traversal's selection
+ *                             on the second stream; 0: the moments behind the
+ *                             narrow waves, the rest on the main stream behind
+ *                             the tile sums (the same F, Z, bit for bit; 0 is
+ *                             also what "spill", "tile_stream" and
+ *                             "trav_front_cur" keep);
+ *   "tile_pass" 0            the tile sums' packed rounds (<= 64 points of
  *                             consecutive small tiles): 1: each lane walks its
  *                             tiles of a round as runs of staged points; 2, 4,
  *                             8: over passes of that many consecutive rounds,
@@ -308,7 +318,10 @@ int tsne_ctx_loop_profile(tsne_ctx *ctx, char *buf, int64_t cap, int64_t *len_ou
  *   "bh.tile_rounds_max", "bh.tile_chunked_waves"  (rep_stats) the most packed
  *                        rounds of one tile_apply wave; the waves that are one
  *                        chunk of a split tile list;
- *   "comm.kind"          the context's communicator: 0 none, 1 RCCL, 2 loopback,
+ *   "bh.narrow_moment_tasks"  (rep_stats) the moment evaluations listed for the
+ *                        narrow groups' queries ("bh.moment_evals" counts the
+ *                        64-query groups' only);
+ *   "comm.kind"         the context's communicator: 0 none, 1 RCCL, 2 loopback,
  *                        3 caller callbacks; "comm.calls" collectives it issued;
  *   "opt.attract_kernel" the optimizer's attraction kernel: 0 attract_rows,
  *                        1 attract_tiles, 2 attract3 (3-D), 3 attract_tiles3

@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--warmup-iters", type=int, default=250)
     ap.add_argument("--show", default="250,700,900")
     ap.add_argument("--marker", default="bbox_partial,bbox3_partial")
+    ap.add_argument("--chain", action="store_true", help="also the traversal-to-tiles chain's start / end offsets")
     a = ap.parse_args()
     rows = sorted(csv.DictReader(open(a.trace)), key=lambda r: int(r["Start_Timestamp"]))
     marks = set(a.marker.split(","))
@@ -56,6 +57,54 @@ def main():
         top = sorted(fams[b].items(), key=lambda kv: -kv[1])[:8]
         print(f"t {100 * b + 1:4d}-{100 * b + 100:4d}: span {sum(spans[b]) / nit / 1e3:8.1f}  " +
               "  ".join(f"{k} {v / nit / 1e3:.0f}" for k, v in top))
+    if a.chain:
+        chain_table(iters, show)
+
+
+# The traversal-to-tiles chain (--chain): offsets from the iteration's first
+# kernel, in us, of the first start ("s") or the last end ("e") of a family
+CHAIN = [("build_qrec", "e"), ("bh_traverse", "s"), ("bh_traverse_narrow", "s"), ("ATCfg", "s"), ("moment_count", "s"),
+         ("bh_traverse", "e"), ("bh_traverse_narrow", "e"), ("moment_reduce", "e"), ("tile_plan", "e"),
+         ("tile_apply", "s"), ("chunk_combine", "e"), ("narrow_moment_apply", "s"), ("narrow_select", "s"),
+         ("reduce_partial", "s"), ("combine_update", "s")]
+
+
+def chain_points(seg):
+    t0 = int(seg[0]["Start_Timestamp"])
+    out = {}
+    for r in seg:
+        f = family(r["Kernel_Name"])
+        s, e = (int(r["Start_Timestamp"]) - t0) / 1e3, (int(r["End_Timestamp"]) - t0) / 1e3
+        out[f, "s"] = min(out.get((f, "s"), s), s)
+        out[f, "e"] = max(out.get((f, "e"), e), e)
+    return out
+
+
+def chain_table(iters, show):
+    head = "  ".join(f"{f[:14]}.{w}" for f, w in CHAIN)
+    print("\nthe chain: offset (us) from the iteration's first kernel of a family's first start (.s) / last end (.e);\n"
+          "gap = tile_apply.s - tile_plan.e, wait = tile_apply.s - bh_traverse.e\n" + " " * 13 + head + "  gap  wait")
+
+    def line(tag, pts):
+        cells = []
+        for (f, w) in CHAIN:
+            v = pts.get((f, w))
+            cells.append(f"{v:{len(f[:14]) + 2}.0f}" if v is not None else " " * (len(f[:14]) + 1) + "-")
+        g = pts.get(("tile_apply", "s"), 0) - pts.get(("tile_plan", "e"), 0)
+        w = pts.get(("tile_apply", "s"), 0) - pts.get(("bh_traverse", "e"), 0)
+        print(f"{tag:13s}" + "  ".join(cells) + f"  {g:5.0f} {w:5.0f}")
+
+    for t, seg in enumerate(iters, start=1):
+        if t in show:
+            line(f"t {t}", chain_points(seg))
+    acc = defaultdict(lambda: defaultdict(list))
+    for t, seg in enumerate(iters, start=1):
+        if ("tile_apply", "s") not in (p := chain_points(seg)):
+            continue   # (the root-tile phase: no traversal)
+        for k, v in p.items():
+            acc[(t - 1) // 100][k].append(v)
+    for b in sorted(acc):
+        line(f"t {100 * b + 1}-{100 * b + 100}", {k: sum(v) / len(v) for k, v in acc[b].items()})
 
 
 if __name__ == "__main__":

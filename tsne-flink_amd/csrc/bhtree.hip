@@ -1121,12 +1121,14 @@ __device__ void narrow_wave(NarrowLDS &L, const double2 *__restrict__ pos, const
     }
     if (STATS && visits) {
         const unsigned long long tv = wave_sum(nvis);
+        const unsigned long long tn = wave_sum((unsigned long long)(k == 0 && c == 0 && valid ? ntask : 0));
         if (lane == 0) {
             atomicAdd(visits, tv);
             atomicAdd(visits + 3, (unsigned long long)npops);
             atomicAdd(visits + 4, (unsigned long long)ntilepts);
             atomicMax(visits + 8, (unsigned long long)npops);
             atomicAdd(visits + 30, 1ull);   // narrow waves run
+            atomicAdd(visits + 46, tn);     // their queries' moment tasks (narrow_moment_apply's)
             const unsigned long long w_end = wall_clock64();
             atomicMax(visits + 15, w_end - w_start);
             atomicMax(visits + 16, ~0ull - w_start);
@@ -2858,6 +2860,9 @@ static void block_order(tsne_ctx *ctx, BHTree &t, const int32_t *cost, int64_t n
 // addresses) and of the work on the stream; nothing else depends on it.
 void bh_alloc(tsne_ctx *ctx, BHTree &t, int64_t n, const std::string &pre) {
     Workspace &ws = ctx->ws;
+    // (a selection still running on the second stream: done before its arrays
+    // are resized or cleared -- bh_alloc_tree ends with a synchronisation)
+    bh_select_join(ctx, t);
     bh_alloc_tree(ctx, t, n, pre);
     // tile_apply slots: traversal waves + at most half as many extra chunks (+ margin)
     const int64_t qwaves = ceil_div(n, 64) + 4;
@@ -3004,6 +3009,21 @@ BHTree &bh_single_tree(tsne_ctx *ctx, int64_t n) {
     return t;
 }
 
+void bh_select_join(tsne_ctx *ctx, BHTree &t) {
+    if (!t.sel_pending) return;
+    t.sel_pending = false;
+    TSNE_HIP(hipStreamWaitEvent(ctx->stream, t.sel_ev, 0));
+}
+
+// moment_count's workgroup size on the moments' own stream (Options::bh_chain):
+// there it is dispatched beside the traversal pair and the attraction, where a
+// 1,024-thread workgroup waits for 16 free wave slots on one CU until their
+// grids thin out (24 us alone, 0.7 - 3.2 ms measured there)
+// (-DMOM_COUNT_CHAIN=1024 for an A/B build)
+#ifndef MOM_COUNT_CHAIN
+#define MOM_COUNT_CHAIN 256
+#endif
+
 void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1,
                   double2 *dF, double *dz, unsigned long long *visits, const int32_t *qlist,
                   unsigned long long *bcost, bool cost_by_label, int32_t *plim) {
@@ -3105,9 +3125,19 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
         if (stream) bh_moments(t, st);
         else mom_late = true;
     }
+    // Options::bh_chain ("Off the chain"): the deferred moments on
+    // their own stream, so that they start with the traversal pair instead of
+    // behind the narrow waves; the narrow waves' moment sums, the hran copy and
+    // narrow_select on the second stream, so that tile_apply .. chunk_combine
+    // and the update run behind nothing narrow.  The options whose kernels read
+    // the selection or the costs on the main stream keep the order of bh_chain 0.
+    const bool chain = o.bh_chain != 0 && o.tile_stream == 0 && o.spill <= 0.0 && o.spill_force == 0 &&
+                       !(o.trav_front_cur > 0.0);
+    const bool mom_own = mom_late && chain && ctx->mom_stream;
+    const hipStream_t mst = mom_own ? ctx->mom_stream : ctx->aux_stream;
     if (mom_late && !narrow) {   // (narrow: its own event below orders the second stream behind the build)
         TSNE_HIP(hipEventRecord(ctx->aux_ev[0], st));
-        TSNE_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_ev[0], 0));
+        if (!mom_own) TSNE_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_ev[0], 0));
     }
     stv.prio = o.trav_prio;   // (also without streaming)
     if (o.trav_front > 0.0 && narrow && t.front_waves == waves) stv.border = t.trav_order;
@@ -3124,16 +3154,33 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
         hipLaunchKernelGGL(nk, dim3(nv.nbn), dim3(256), 0, ctx->aux_stream, t.pos, t.dupc, t.nodes, t.qrec, t.ttask_n,
                            t.meta, t.mom_flag, mom_tol, theta, s0, s1, qlist, (int32_t)t.n, dF, dz, visits, bcost,
                            t.tcost, clab, nv);
-        TSNE_HIP(hipEventRecord(ctx->aux_ev[1], ctx->aux_stream));
+        if (!chain) TSNE_HIP(hipEventRecord(ctx->aux_ev[1], ctx->aux_stream));
     }
     hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64 * TRAV_WPB), 0, st, t.pos, t.dupc, t.nodes, t.qrec, t.ttask, t.ttask_n,
                        t.meta, t.mom_flag, mom_tol, theta, s0, s1, qlist, (int32_t)t.n, dF, dz, visits, bcost, t.wcost,
                        t.tcost, clab, nv, plim, sv, stv);
     if (mom_late) {
-        bh_moments(t, ctx->aux_stream);
+        // (their own stream: behind the build by the event recorded in front of the traversal pair)
+        if (mom_own) TSNE_HIP(hipStreamWaitEvent(mst, ctx->aux_ev[0], 0));
+        bh_moments(t, mst, mom_own ? MOM_COUNT_CHAIN : 1024);
         if (!t.mom_ev) TSNE_HIP(hipEventCreateWithFlags(&t.mom_ev, hipEventDisableTiming));
-        TSNE_HIP(hipEventRecord(t.mom_ev, ctx->aux_stream));
+        TSNE_HIP(hipEventRecord(t.mom_ev, mst));
     }
+    if (chain && narrow) {
+        // the narrow waves' moment sums: behind the narrow kernel (this stream)
+        // and the moments; they and the 64-query chain (tile_apply, moment_apply,
+        // chunk_combine) write disjoint F, Z entries -- a narrow group has no
+        // tiles (bh_traverse zeroes its ttask_n / tcost and leaves), so its
+        // partial sums are zeros, which chunk_combine does not add
+        if (mom_late) TSNE_HIP(hipStreamWaitEvent(ctx->aux_stream, t.mom_ev, 0));
+        hipLaunchKernelGGL(narrow_moment_apply, dim3(ceil_div(t.nar_hmax * 64, 256)), dim3(256), 0, ctx->aux_stream, t.pos,
+                           t.nodes, t.mom, t.hlist, t.hcount, t.nmtask, t.nmtask_n, s0, s1, qlist, dF, dz);
+        TSNE_HIP(hipMemcpyAsync(t.hran, t.hcount, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->aux_stream));
+        TSNE_HIP(hipEventRecord(ctx->aux_ev[1], ctx->aux_stream));
+    }
+    // (narrow_select on the second stream, below: once bh_traverse has written wcost)
+    const bool sel_off = chain && nfac > 0.0 && !plim;
+    if (sel_off) TSNE_HIP(hipEventRecord(ctx->aux_ev[2], st));
     if (stream) {   // the consumers beside the traversal, then their moments and sums into F, Z
         // (tile_stream_gate: dispatched once every traversal block has started,
         // so that they take the slots its tail frees, not slots its blocks need)
@@ -3219,20 +3266,34 @@ void bh_repulsion(tsne_ctx *ctx, BHTree &t, double theta, int64_t s0, int64_t s1
     }
     // the narrow waves' own queries from here on (their F / Z entries are
     // disjoint from the 64-query waves' above, so the tiles did not wait for them)
+    // (bh_chain: their moment sums and the hran copy ran there too, in front of the event)
     if (narrow) {
         TSNE_HIP(hipStreamWaitEvent(st, ctx->aux_ev[1], 0));
-        hipLaunchKernelGGL(narrow_moment_apply, dim3(ceil_div(t.nar_hmax * 64, 256)), dim3(256), 0, st, t.pos,
-                           t.nodes, t.mom, t.hlist, t.hcount, t.nmtask, t.nmtask_n, s0, s1, qlist, dF, dz);
-        TSNE_HIP(hipMemcpyAsync(t.hran, t.hcount, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        if (!chain) {
+            hipLaunchKernelGGL(narrow_moment_apply, dim3(ceil_div(t.nar_hmax * 64, 256)), dim3(256), 0, st, t.pos,
+                               t.nodes, t.mom, t.hlist, t.hcount, t.nmtask, t.nmtask_n, s0, s1, qlist, dF, dz);
+            TSNE_HIP(hipMemcpyAsync(t.hran, t.hcount, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        }
     }
     // the next traversal's heavy groups (of the same query count) from this one's costs
+    // (bh_chain: on the second stream -- behind the narrow waves' ncost and the
+    // readers of hlist / hcount above by its order, behind bh_traverse's wcost
+    // and nflag reads by the event; nothing on the main stream reads what it
+    // writes before the tree's next build, which joins it: bh_select_join)
     if (nfac > 0.0 && !plim) {
-        if (!narrow) TSNE_HIP(hipMemsetAsync(t.nflag, 0, sizeof(int32_t) * waves, st));   // no stale slots
+        const hipStream_t ss = sel_off ? ctx->aux_stream : st;
+        if (sel_off) TSNE_HIP(hipStreamWaitEvent(ss, ctx->aux_ev[2], 0));
+        if (!narrow) TSNE_HIP(hipMemsetAsync(t.nflag, 0, sizeof(int32_t) * waves, ss));   // no stale slots
         const bool front = o.trav_front > 0.0;
         if (front) t.trav_order = ctx->ws.get<int32_t>(t.pre + "trav_order", ceil_div(t.tile_waves, TRAV_WPB) + 1);
-        hipLaunchKernelGGL(narrow_select, dim3(1), dim3(1024), 0, st, t.wcost, waves, t.nflag, t.ncost, t.hlist,
+        hipLaunchKernelGGL(narrow_select, dim3(1), dim3(1024), 0, ss, t.wcost, waves, t.nflag, t.ncost, t.hlist,
                            t.hcount, t.nar_hmax, nfac, std::min<int64_t>(t.nar_hmax, narrow_fill(ctx, waves)),
                            front ? t.trav_order : nullptr, o.trav_front);
+        if (sel_off) {
+            if (!t.sel_ev) TSNE_HIP(hipEventCreateWithFlags(&t.sel_ev, hipEventDisableTiming));
+            TSNE_HIP(hipEventRecord(t.sel_ev, ss));
+            t.sel_pending = true;
+        }
         t.sel_waves = waves;
         t.front_waves = front ? waves : 0;
     } else {
@@ -3277,6 +3338,7 @@ bool repulsion_stat(tsne_ctx *ctx, const std::string &name, int64_t *value_out) 
         atk = (name[14] == '1' ? 38 : 41) + (name[16] == '2' ? 0 : name[16] == '4' ? 1 : 2);
     if (name == "bh.tile_rounds_max") atk = 44;
     if (name == "bh.tile_chunked_waves") atk = 45;
+    if (name == "bh.narrow_moment_tasks") atk = 46;   // moment tasks of the narrow groups' queries
     if (atk < 0 || atk >= VIS_N) return false;
     TSNE_REQUIRE(ctx->opts.rep_stats && ctx->ws.has("rep.visits"), "counter '" + name + "' needs option rep_stats");
     unsigned long long v[VIS_N];

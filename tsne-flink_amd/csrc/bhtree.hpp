@@ -212,7 +212,19 @@ struct BHTree {
     // call (bh_repulsion runs them on the second stream beside the traversal)
     bool mom_deferred = false;
     hipEvent_t mom_ev = nullptr;
-    bool ran_stream = false;              // the last traversal streamed its lists
+    // Options::bh_chain: narrow_select runs on the second stream; sel_ev is its
+    // end, which the main stream joins before the tree's next build
+    // (bh_select_join) while sel_pending
+    hipEvent_t sel_ev = nullptr;
+    bool sel_pending = false;
+    BHTree() = default;
+    BHTree(const BHTree &) = delete;
+    BHTree &operator=(const BHTree &) = delete;
+    ~BHTree() {   // the tree's events (its arrays are the context workspace's)
+        for (hipEvent_t e : {ord_ev, mom_ev, sel_ev})
+            if (e) (void)hipEventDestroy(e);
+    }
+    bool ran_stream = false;             // the last traversal streamed its lists
     std::string pre;                      // the workspace prefix of this tree's buffers
 };
 
@@ -235,6 +247,11 @@ BHTree &bh_single_tree(tsne_ctx *ctx, int64_t n);
 void bh_build(tsne_ctx *ctx, BHTree &t, const double *dY, double theta, const int32_t *rowmap = nullptr,
               bool root_tile_ok = false, double near_tol = -1.0);
 double bh_near_tol(const tsne_ctx *ctx, bool late);
+// The main stream behind the tree's last narrow_select where that ran on the
+// second stream (Options::bh_chain): before anything that reads or rewrites
+// the selection (nflag, hlist, hcount, wcost, trav_order) -- the head of
+// bh_build and of bh_alloc.  Nothing is enqueued when none is pending.
+void bh_select_join(tsne_ctx *ctx, BHTree &t);
 // Repulsion for the query slots [s0, s1): sorted positions, or with qlist
 // (device, ascending sorted positions: one rank's own queries) the positions
 // qlist[s0..s1).  F (double2) and z (sum of Q) are written at the sorted

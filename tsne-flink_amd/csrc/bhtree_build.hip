@@ -1294,10 +1294,10 @@ double bh_near_dmax(double theta, double tol) {
 
 // moment_count reads the nodes' cnt (after dup_apply's corrections),
 // moment_items their bottom-up boxes: after the whole build, on stream ms
-void bh_moments(BHTree &t, hipStream_t ms) {
+void bh_moments(BHTree &t, hipStream_t ms, int count_threads) {
     const int64_t n = t.n;
-    hipLaunchKernelGGL(moment_count, dim3(ceil_div(n + 1, 1024)), dim3(1024), 0, ms, t.nodes, n, t.meta, t.mom_flag,
-                       t.mom_cnt, t.mom_list, t.meta, t.mom_off, t.mom_item);
+    hipLaunchKernelGGL(moment_count, dim3(ceil_div(n + 1, count_threads)), dim3(count_threads), 0, ms, t.nodes, n, t.meta,
+                       t.mom_flag, t.mom_cnt, t.mom_list, t.meta, t.mom_off, t.mom_item);
     const int mgrid = (int)std::min<int64_t>(2048, std::max<int64_t>(1, ceil_div(n, 256)));
     hipLaunchKernelGGL(moment_items<true>, dim3(mgrid), dim3(256), 0, ms, t.pos, t.nodes, t.mom_off, n, t.mom_item,
                        t.mom_part, t.mom_cnt, t.mom);
@@ -1311,6 +1311,11 @@ void bh_build(tsne_ctx *ctx, BHTree &t, const double *dY, double theta, const in
     t.near_dmax = bh_near_dmax(theta, near_tol);
     hipStream_t st = ctx->stream;
     const int64_t n = t.n;
+    // the previous traversal's selection (second stream with Options::bh_chain)
+    // is read from here on: trav_order_cur below, the next traversal pair.  At
+    // the build's head the join is off both the iteration's chain and the
+    // build -> traversal gap
+    bh_select_join(ctx, t);
     t.rowmap = rowmap;
     t.root_tile = false;
     t.mom_deferred = false;

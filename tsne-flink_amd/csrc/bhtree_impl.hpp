@@ -77,8 +77,10 @@ __device__ __forceinline__ void box_centre(const BHNode &nd, double &cx, double 
 }  // namespace
 
 // The subtree moments of a finished build on stream ms: bh_repulsion launches
-// the ones bh_build deferred (Options::build_fuse).
-void bh_moments(BHTree &t, hipStream_t ms);
+// the ones bh_build deferred (Options::build_fuse).  count_threads:
+// moment_count's workgroup size (a multiple of 64, <= 1024; the moments do
+// not depend on it, only the placement of the nodes' item ranges).
+void bh_moments(BHTree &t, hipStream_t ms, int count_threads = 1024);
 
 // The build's share of bh_alloc, in its place in the allocation order: the
 // tree's own buffers (ends with a stream synchronisation: mom_flag's initial

@@ -164,6 +164,7 @@ static const OptionField k_options[] = {
     {"bu_acqrel", nullptr, &Options::bu_acqrel, 0, 1},
     {"bh_split", nullptr, &Options::bh_split, 0, 1},
     {"build_fuse", nullptr, &Options::build_fuse, 0, 1},
+    {"bh_chain", nullptr, &Options::bh_chain, 0, 1},
     {"tile_pass", nullptr, &Options::tile_pass, 0, 8},
     {"tile_prefetch", nullptr, &Options::tile_prefetch, 0, 1},
     {"transform_resort", nullptr, &Options::transform_resort, 0, 1 << 30},
@@ -320,6 +321,7 @@ int tsne_ctx_create(int32_t device, tsne_ctx **out) {
         c->own_stream = true;
         TSNE_HIP(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
         for (auto &e : c->aux_ev) TSNE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        TSNE_HIP(hipStreamCreateWithFlags(&c->mom_stream, hipStreamNonBlocking));
         TSNE_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->pinned), 64 * sizeof(int32_t)));
         *out = c.release();
     });
@@ -371,6 +373,9 @@ int tsne_ctx_destroy(tsne_ctx *ctx) {
     int rc = guard([&] {
         DeviceGuard g(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
+        // (the trees' events are released with the trees below: nothing of theirs still queued)
+        if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
+        if (ctx->mom_stream) (void)hipStreamSynchronize(ctx->mom_stream);
         opt_destroy(ctx);
         transform_destroy(ctx);
         delete ctx->single_tree;
@@ -383,6 +388,8 @@ int tsne_ctx_destroy(tsne_ctx *ctx) {
         if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
         if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
         if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
+        if (ctx->mom_stream) (void)hipStreamSynchronize(ctx->mom_stream);
+        if (ctx->mom_stream) (void)hipStreamDestroy(ctx->mom_stream);
         for (auto &e : ctx->aux_ev)
             if (e) (void)hipEventDestroy(e);
         if (ctx->st_stream) (void)hipStreamSynchronize(ctx->st_stream);

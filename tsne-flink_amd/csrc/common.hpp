@@ -237,6 +237,10 @@ struct Options {
     int trav_prio = 0;           // 1-3: the 64-query BH traversal's waves at that issue priority (s_setprio)
     int trav_burst = 1;          // the 64-query BH traversal reads a popped record's fields in bursts (0: one by
                                  // one, at first use); the same bits either way
+    int bh_chain = 1;            // 2-D BH: the deferred moments on a stream of their own beside the traversal pair, the
+                                 // narrow waves' moment sums and the next selection on the second stream, off the
+                                 // traversal -> tiles -> update chain (0: the moments behind the narrow waves, the
+                                 // rest on the main stream; the same bits)
     int tile_stream_gate = 1;    // 1: the consumers wait (on the device) until every traversal block has started
     int transform_resort = 10;   // transform steps between Morton sorts of the new points (0: only at setup; no
                                  // result depends on it, transform.hip "Canonical order")
@@ -253,7 +257,9 @@ struct tsne_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipStream_t aux_stream = nullptr;   // second stream of one operator (the narrow BH waves)
-    hipEvent_t aux_ev[2] = {nullptr, nullptr};
+    hipEvent_t aux_ev[3] = {nullptr, nullptr, nullptr};   // [0] the build done, [1] the narrow waves' F, Z final,
+                                                          // [2] bh_traverse done (Options::bh_chain)
+    hipStream_t mom_stream = nullptr;   // the subtree moments a build deferred, beside the traversal (Options::bh_chain)
     // third stream: the tile-streaming consumers (created on first use)
     hipStream_t st_stream = nullptr;
     hipEvent_t st_ev[3] = {nullptr, nullptr, nullptr};

@@ -727,6 +727,9 @@ void opt_destroy(tsne_ctx *ctx) {
         (void)hipStreamSynchronize(s->side);
         (void)hipStreamDestroy(s->side);
     }
+    // (the tree's last narrow_select may still run there, Options::bh_chain: done
+    // before a next optimizer clears the same workspace arrays)
+    if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
     delete ctx->opt;
     ctx->opt = nullptr;
 }
